@@ -35,7 +35,7 @@ against ott itself.
 
 Pins against the reference's own printed outputs (wasserstein-computation
 .ipynb on the stored python/mcmc_runs/diamonds-example-*.pkl, extracted
-byte-wise into tests/golden/diamonds_example.npz):
+byte-wise into tests/golden/diamonds_example_*.npz):
   * pth_moment_rmse: cell 12's 3.4000627994537354 is reproduced to rel 2e-6
     on the device (tests/test_gpu_eval.py) from the stored references and
     cell 10's printed samples moments.  The notebook's value is the

@@ -9,12 +9,19 @@ N = 1 (BASELINE configs[1]): ARWMH.sample, per-chain adaptation (the
   sample() API contract).  Roofline: HBM, B_A(64) = 17,712 B per chain-step.
 N > 1 (BASELINE configs[4]): pooled-covariance ARWMH, 65,536 chains per GPU
   (weak scaling), all-reduce(sum) of the pooled sums over RCCL every step and
-  a shared refactorisation on every rank (kernels_amd/pooled.py).  Sub-fields:
-  the same with pooling every 16 steps, with the all-reduce overlapped
+  a shared refactorisation on every rank (kernels_amd/pooled.py).  Sub-fields
+  (--full): the same with pooling every 16 steps, with the all-reduce overlapped
   (lag-one pooling), the strong-scaling forms (524,288 chains in total), and
   regime A (no collective).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: it sets up, warms up,
+times the K steps and prints the result line.  `--full` adds every other leg
+to the line (the fused launch, the pooled / strong-scaling / regime A
+sub-fields, ESS/s, the CPU baseline).  `--dump-outputs DIR` (one GPU) writes
+the state the last timed step returned as DIR/<leaf>.npy; with the same
+arguments the inputs, and so these arrays, are the same from run to run.
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script
 starts its N ranks itself, as child processes, before anything touches a
@@ -225,8 +232,10 @@ def clock_warm(step, ctx, seconds: float = CLOCK_WARM_S):
     an idle gap the GPU needs ~30 ms (~100 launches) of back-to-back step
     launches to reach its steady clocks (tools/ramp.py: 0.30-0.34 ms per
     launch at first, 0.258 ms after), so a 5-step warmup times
-    the ramp, not the kernel.  These are real transitions: the chains just
-    advance further before the timed steps.  Reported as `clock_warm`."""
+    the ramp, not the kernel.  These are real transitions; their number
+    depends on the wall clock, so the headline leg runs them on a copy of its
+    state (leg_regime_a), and the pooled legs' chains just advance further
+    before the timed steps.  Reported as `clock_warm`."""
     import torch
     t0 = time.perf_counter()
     n = 0
@@ -243,9 +252,12 @@ def clock_warm(step, ctx, seconds: float = CLOCK_WARM_S):
 
 def leg_regime_a(ctx, g, C, off, steps, warmup):
     """ARWMH.sample per step (per-chain adaptation); HIP events on the launch
-    stream bracket the step launches only."""
+    stream bracket the step launches only.  The clock warm-up's launches (a
+    wall-clock count) advance a copy of the state, so `state` is `warmup` +
+    `steps` transitions from the seeded start whatever the clock did."""
     import torch
     from kernels_amd import ARWMH, PRNGKey
+    from kernels_amd.arwmh import _clone_state
     d = g.dim
     k = ARWMH(potential_fn=g, num_chains=C, device=ctx.dev, chain_offset=off)
     gen = torch.Generator(device=ctx.dev)
@@ -254,7 +266,9 @@ def leg_regime_a(ctx, g, C, off, steps, warmup):
     st = k.init(PRNGKey(0), 0, z0, (), {})
     for _ in range(warmup):
         k.sample_(st, 1)
-    warm = clock_warm(lambda: k.sample_(st, 1), ctx)
+    stw = _clone_state(st)
+    warm = clock_warm(lambda: k.sample_(stw, 1), ctx)
+    del stw
     stream = torch.cuda.current_stream(ctx.dev)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -267,6 +281,50 @@ def leg_regime_a(ctx, g, C, off, steps, warmup):
     wall = timed_region(ctx, run)
     kern_ms = ev0.elapsed_time(ev1) / steps
     return dict(wall=wall, kern_ms=kern_ms, kernel=k, state=st, clock_warm=warm)
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6  # all files of one --dump-outputs together stay under 64 MB
+
+
+def dump_outputs(path: str, st) -> dict:
+    """Write the leaves of the state the last timed step returned (what a
+    caller of sample() receives) as `path`/<leaf>.npy: float leaves as
+    float32, `i` and `rng_key` (its uint32 bits) as float64, exactly.  The
+    smallest leaves are written whole; a leaf that would take more than an
+    equal share of what is left of the budget (the packed `scale` at the
+    default shape) is written for a fixed sample of chains: the sorted first n
+    of default_rng(0).permutation(C).  Returns {leaf: rows written}."""
+    import torch
+    a = st.adapt_state
+    leaves = {"i": st.i, "z": st.z, "potential_energy": st.potential_energy,
+              "mean_accept_prob": st.mean_accept_prob, "loc": a.loc, "scale": a.scale,
+              "log_step_size": a.log_step_size, "as_change": st.as_change, "rng_key": st.rng_key}
+    exact64 = ("i", "rng_key")
+    C = st.z.shape[0]
+    perm = np.random.default_rng(0).permutation(C)
+    os.makedirs(path, exist_ok=True)
+
+    def nbytes(name):
+        return leaves[name].numel() * (8 if name in exact64 else 4)
+
+    left, written = DUMP_BUDGET_BYTES, {}
+    order = sorted(leaves, key=nbytes)
+    for n_done, name in enumerate(order):
+        t = leaves[name]
+        share = left // (len(order) - n_done)
+        rows = C
+        if nbytes(name) > share:
+            rows = max(1, share // (nbytes(name) // C))
+            idx = np.sort(perm[:rows])
+            t = t[torch.as_tensor(idx, dtype=torch.int64, device=t.device)]
+        x = t.cpu().numpy()
+        if name == "rng_key":
+            x = x.view(np.uint32)
+        x = x.astype(np.float64 if name in exact64 else np.float32)
+        np.save(os.path.join(path, name + ".npy"), x)
+        left -= x.nbytes
+        written[name] = rows
+    return written
 
 
 def leg_pooled(ctx, g, C, off, steps, warmup, K=1, overlap=False, burn_in=0):
@@ -686,11 +744,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--chains", type=int, default=65536, help="chains per GPU (weak scaling)")
     ap.add_argument("--dim", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ess", action="store_true")
-    ap.add_argument("--no-pooled", action="store_true", help="N = 1: skip the pooled sub-fields")
-    ap.add_argument("--no-extra", action="store_true", help="headline leg only (profiling runs)")
-    ap.add_argument("--no-fused", action="store_true", help="skip the fused 50-step launch (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: the fused launch, the pooled / strong-scaling / "
+                         "regime A sub-fields, ESS/s and the CPU baseline (the --no-* switches drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--gpus 1: after the timed steps, write the state the last one returned as DIR/<leaf>.npy "
+                         "(float32 / float64, under 64 MB in all; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full / --configs: skip the CPU baseline")
+    ap.add_argument("--no-ess", action="store_true", help="--full: skip the ESS leg")
+    ap.add_argument("--no-pooled", action="store_true", help="--full, N = 1: skip the pooled sub-fields")
+    ap.add_argument("--no-extra", action="store_true", help="headline leg only, whatever --full says")
+    ap.add_argument("--no-fused", action="store_true", help="--full: skip the fused 50-step launch")
     ap.add_argument("--configs", nargs="?", const=",".join(CONFIG_NAMES), default=None,
                     help="per-config lines instead of the headline (comma list; default all): " + ",".join(CONFIG_NAMES))
     args = ap.parse_args()
@@ -703,6 +767,10 @@ def main():
         return configs_main(args.configs.split(","), args.steps if args.steps != 200 else 20)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.gpus != 1:
+        raise SystemExit("--dump-outputs writes the one-GPU headline's state: run it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -715,7 +783,7 @@ def main():
     d, C = args.dim, args.chains
     world, rank = ctx.world, ctx.rank
     g = P.correlated_gaussian(d)
-    extra = not args.no_extra
+    extra = args.full and not args.no_extra
     data = "synthetic (64-d correlated Gaussian, kappa=1e2, default_rng(64) rotation)"
     metric = "chain-steps/sec (whole node) + ESS/sec, 64-dim Gaussian"
 
@@ -732,6 +800,7 @@ def main():
                     "traffic_same_build": traffic[2] if traffic else None, "kernel_ms": r["kern_ms"],
                     "kernel": step_kernel_name(d),
                     "algorithmic_bytes_per_launch": per_launch_bytes}
+        dumped = dump_outputs(args.dump_outputs, r["state"]) if args.dump_outputs is not None else None
         fused = None
         if extra and not args.no_fused:
             k, st = r["kernel"], r["state"]
@@ -757,6 +826,8 @@ def main():
                            "chains_per_gpu": C, "dim": d, "parallelism": "1 GPU"},
                 "roofline": roofline, "cpu_baseline": cpu, "clock_warm": r["clock_warm"], "ess": ess,
                 "fused_chain_steps_per_s": fused, **sub}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
         print(json.dumps(line), flush=True)
         return
 

@@ -1,9 +1,10 @@
 """Extract the raw float32 buffers of the reference's stored diamonds runs
 into a data-only fixture, WITHOUT unpickling anything.
 
-Sources (reference data files, read as bytes):
-  /root/reference/python/mcmc_runs/diamonds-example-references.pkl
-  /root/reference/python/mcmc_runs/diamonds-example-samples.pkl
+Sources (data files of a checkout of the reference, read as bytes; they are
+pickles and are not stored here, only the arrays extracted from them are):
+  <reference>/python/mcmc_runs/diamonds-example-references.pkl
+  <reference>/python/mcmc_runs/diamonds-example-samples.pkl
 
 They are the inputs of python/jupyter/wasserstein-computation.ipynb (cells
 7-38), whose printed outputs are the only reference outputs that exist for
@@ -27,10 +28,11 @@ reference no longer holds.
 
 Column order: the notebook builds `references` / `samples` from the combined
 frame's columns b[1..24], Intercept, sigma (cell 10 prints the E[X^2] table in
-that order), so the fixture stores (10000, 26) matrices in that order.  The
-cell-10 table is checked here before anything is written.
+that order), so the fixture stores (10000, 26) matrices in that order, one
+file per draw set (`load_fixture` reads both).  The cell-10 table is checked
+here before anything is written.
 
-  python tests/golden/extract_diamonds_pkl.py   ->  tests/golden/diamonds_example.npz
+  python tests/golden/extract_diamonds_pkl.py <reference>   ->  tests/golden/diamonds_example_{references,samples}.npz
 """
 import os
 import pickletools
@@ -39,8 +41,8 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = "/root/reference/python/mcmc_runs/diamonds-example-{}.pkl"
-OUT = os.path.join(HERE, "diamonds_example.npz")
+SRC = os.path.join("python", "mcmc_runs", "diamonds-example-{}.pkl")  # below the reference's root
+OUT = os.path.join(HERE, "diamonds_example_{}.npz")
 
 # wasserstein-computation.ipynb cell 10: E[|X|^2] per column (reference, samples)
 CELL10 = {
@@ -147,8 +149,8 @@ def _array(node) -> np.ndarray:
     return np.frombuffer(bytes(raw), dtype="<f4").reshape(shape).astype(np.float32)
 
 
-def load(which: str) -> dict:
-    with open(SRC.format(which), "rb") as f:
+def load(root: str, which: str) -> dict:
+    with open(os.path.join(root, SRC.format(which)), "rb") as f:
         data = f.read()
     return {k: _array(v) for k, v in _inert_eval(data).items()}
 
@@ -174,9 +176,19 @@ def cell10_mismatch(x: np.ndarray, side: int):
     return bad
 
 
+def load_fixture():
+    """(references, samples, column names) of the stored fixture files."""
+    r = np.load(OUT.format("references"))
+    s = np.load(OUT.format("samples"))
+    assert list(r["columns"]) == list(s["columns"])
+    return r["references"], s["samples"], [str(c) for c in r["columns"]]
+
+
 def main():
-    ref = matrix(load("references"))
-    smp = matrix(load("samples"))
+    if len(sys.argv) != 2:
+        sys.exit("usage: extract_diamonds_pkl.py <root of a checkout of the reference>")
+    ref = matrix(load(sys.argv[1], "references"))
+    smp = matrix(load(sys.argv[1], "samples"))
     assert ref.shape == smp.shape == (10000, 26)
     bad = cell10_mismatch(ref, 0)
     if bad:
@@ -186,8 +198,9 @@ def main():
     # samples-dependent printed value (cells 12, 19, 21-24, 38, 31) is
     # unreachable from the files the reference holds.  Recorded, not fatal.
     bad_s = cell10_mismatch(smp, 1)
-    np.savez_compressed(OUT, references=ref, samples=smp, columns=np.array(COLUMNS))
-    print(f"wrote {OUT}: references {ref.shape} reproduce cell 10 (26/26 columns); "
+    np.savez_compressed(OUT.format("references"), references=ref, columns=np.array(COLUMNS))
+    np.savez_compressed(OUT.format("samples"), samples=smp, columns=np.array(COLUMNS))
+    print(f"wrote {OUT.format('*')}: references {ref.shape} reproduce cell 10 (26/26 columns); "
           f"stored samples differ from the notebook's in {len(bad_s)}/26 columns")
 
 

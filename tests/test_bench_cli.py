@@ -37,6 +37,17 @@ def test_configs_names_checked_before_any_gpu_call():
     assert r.returncode != 0
 
 
+def test_full_and_dump_outputs_options(tmp_path):
+    """--full is an option of every run shape; --dump-outputs belongs to the
+    one-GPU headline and is refused for more ranks before anything starts."""
+    r = _run(["--gpus", "3", "--full"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
+    assert r.returncode != 0 and "--gpus 3 but WORLD_SIZE=2" in (r.stderr + r.stdout)  # parsed, then the rank check
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--dump-outputs", str(out)], {})
+    assert r.returncode != 0 and "--gpus 1" in (r.stderr + r.stdout)
+    assert not out.exists()
+
+
 def test_library_overrides_refused():
     """Any AMH_* variable (a library path, the diagnostic build's A/B
     switches) stops the bench before it touches a GPU: the line always

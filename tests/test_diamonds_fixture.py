@@ -1,4 +1,4 @@
-"""The reference's stored diamonds draws (tests/golden/diamonds_example.npz,
+"""The reference's stored diamonds draws (tests/golden/diamonds_example_*.npz,
 extracted byte-wise by tests/golden/extract_diamonds_pkl.py) against the
 outputs python/jupyter/wasserstein-computation.ipynb prints for them.
 
@@ -31,8 +31,7 @@ CELL12 = 3.4000627994537354
 
 @pytest.fixture(scope="module")
 def fx():
-    z = np.load(os.path.join(HERE, "golden", "diamonds_example.npz"))
-    return z["references"], z["samples"], [str(c) for c in z["columns"]]
+    return X.load_fixture()
 
 
 def test_columns_and_shapes(fx):
@@ -66,10 +65,3 @@ def test_synthetic_diamonds_centre_is_the_reference_draw_mean(fx):
     import posteriors as P
     ref, _, _ = fx
     np.testing.assert_allclose(P._DIAMONDS_B_HEAD, ref[:, :4].astype(np.float64).mean(0), atol=5e-4)
-
-
-@pytest.mark.skipif(not os.path.exists(X.SRC.format("references")), reason="reference files absent (GPU box)")
-def test_extraction_reproduces_fixture(fx):
-    ref, smp, _ = fx
-    np.testing.assert_array_equal(X.matrix(X.load("references")), ref)
-    np.testing.assert_array_equal(X.matrix(X.load("samples")), smp)

@@ -137,11 +137,12 @@ def test_sinkhorn_unbiased_and_exact_limit(gpu):
     assert exact - 1e-4 <= r["cost"] <= exact + 0.01 * np.log(200) + 1e-4
 
 
-# ---- the reference's stored diamonds draws (tests/golden/diamonds_example.npz) --
+# ---- the reference's stored diamonds draws (tests/golden/diamonds_example_*.npz) --
 def _diamonds_fixture():
-    import os
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "diamonds_example.npz"))
-    return z["references"], z["samples"]
+    import sys, os
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import extract_diamonds_pkl as X
+    return X.load_fixture()[:2]
 
 
 def test_pth_moment_rmse_pins_notebook_cell12(gpu):

@@ -4,9 +4,9 @@ Inputs (gpurun_out/prof_<tag>/): rocprofv3 --kernel-trace --stats of
 `bench.py --steps S --warmup W` and two --pmc passes (FETCH_SIZE,
 WRITE_SIZE) of `bench.py --steps S2 --warmup W2`.  The step-kernel launches
 of bench.py come in order: W warmup, the clock-warm launches (a fixed wall
-time, so a variable count), S timed single-step launches, then (default
-command) one fused 50-step launch and the ESS leg's launches; the S launches
-before the first long (fused) launch are summarised.
+time, so a variable count), S timed single-step launches, then (with
+--full) one fused 50-step launch and the ESS leg's launches; the S launches
+before the first long (fused) launch, or the last S, are summarised.
 
 HBM traffic per launch (MI355X_MICROARCH.md, HBM section): FETCH_SIZE and
 WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE counts half the bytes of wide
