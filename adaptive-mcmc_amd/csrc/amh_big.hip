@@ -35,9 +35,6 @@ namespace {
 
 constexpr int kNSMAX = 4;  // row slots per lane: d <= 64 * NS, NS = 2 (d <= 128) or 4
 constexpr int kAsssBigMaxIter = 50;  // asss.py:59 max_iterations
-#ifndef AMH_ABL_NOPASSD
-#define AMH_ABL_NOPASSD 0
-#endif
 
 __device__ __forceinline__ float rdl(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -143,13 +140,8 @@ __device__ __forceinline__ void for_columns(const float* Lc, int d, int64_t P, f
         for (int q = 0; q < qn; ++q) {
           float v[NS];
           static_for<NS>([&](auto K) { v[K] = vn[K]; });
-#if AMH_BIG_NOPIPE
-          f(KB, kColBlk * b + q, v);
-          if (q + 1 < qn) rd(q + 1, vn);
-#else
           if (q + 1 < qn) rd(q + 1, vn);
           f(KB, kColBlk * b + q, v);
-#endif
           if constexpr (NS == 3) { lds_wait(vn[0], vn[1], vn[2]); } else { lds_wait_n(vn); }
         }
       }
@@ -657,7 +649,6 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
     hv[K] = e[K] * v[K];
     y[K] = av[K] = ty[K] = tv[K] = wy[K] = wv[K] = 0.0f;
   });
-#if !AMH_ABL_NOPASSA
   for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
     constexpr int kb = KB;
     const int jl = j - 64 * kb;
@@ -691,7 +682,6 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
       }
     });
   });
-#endif
   float svr[NS];  // S v for the raw draw
   static_for<NS>([&](auto K) { svr[K] = av[K] + epsd * v[K]; });
   // ---- stereographic projection, tangent v (asss.py:40-45, 219-222)
@@ -725,7 +715,6 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
     Pa[K] = Pb[K] = Pg[K] = 0.0f;
   });
   // ---- P a, P b, P g: row k of P (= column k) coalesced, k in order
-#if !AMH_ABL_NOPMV  // (timing ablations only: AMH_ABL_*)
   static_for<NS>([&](auto KB) {
     constexpr int kb = KB;
     if (64 * kb < d) {
@@ -749,7 +738,6 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
       }
     }
   });
-#endif
   // the point at angle (cs, sn) of the slice circle: x and U
   auto eval = [&](float cs, float sn, float (&xo)[NS], float& om) -> float {
     om = 1.0f - ((zd * cs) + (vd * sn));
@@ -858,7 +846,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
         bad = bad || (act && amh_isnan(dnew));
       });
     }
-    const bool revert = __ballot(bad) != 0ull || AMH_ABL_NOPASSD;
+    const bool revert = __ballot(bad) != 0ull;
     float sdiff = 0.0f;
     if (!revert) {
       // pass D: the update, L' streamed out (in place allowed: block b + 1 is
@@ -896,7 +884,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
         });
       });
       sdiff = sqrtf(big_sum(sacc));
-    } else if (Lout != Lc && !AMH_ABL_NOPASSD) {  // factor kept (asss.py:255): copied verbatim
+    } else if (Lout != Lc) {  // factor kept (asss.py:255): copied verbatim
       for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
         constexpr int kb = KB;
         float* ocol = Lout + col_off(d, j) - j;
@@ -1140,10 +1128,7 @@ bool pooled_big_model(int model_id, int d) {
 
 // row slots per lane by d: two up to 128, three up to 192, four up to 256
 // (each a separate instantiation; big_sum adds the absent slots as +0)
-#ifndef AMH_BIG_NS3
-#define AMH_BIG_NS3 1
-#endif
-static int row_slots(int d) { return d <= 128 ? 2 : ((AMH_BIG_NS3 && d <= 192) ? 3 : 4); }
+static int row_slots(int d) { return d <= 128 ? 2 : d <= 192 ? 3 : 4; }
 static int wave_grid(int64_t n) {
   int64_t b = (n + 3) / 4;
   if (b > 256 * 16) b = 256 * 16;

@@ -33,26 +33,7 @@ namespace amh {
 // without (tools/u64_timeline.py, r4p).  The last arriver reads the sums with
 // agent-scope (sc1) loads only; with sc1 stores drained before every add that
 // is the guide's write-through hand-off, which needs no acquire fence (round
-// 6: the buffer_inv removed, AMH_HANDOFF_FENCE=1 restores it).  Diagnostic
-// variant -DAMH_TICKET_ACQREL: the acquire-release RMW instead.
-#ifdef AMH_TICKET_ACQREL
-#define AMH_TICKET_ORDER __ATOMIC_ACQ_REL
-#else
-#define AMH_TICKET_ORDER __ATOMIC_RELAXED
-#endif
-#ifndef AMH_HANDOFF_FENCE
-#define AMH_HANDOFF_FENCE 0
-#endif
-
-// fused stats kernel, drawn-ahead noise rows loaded early (diagnostic
-// variants; measured at C = 65,536, r4h): AMH_F64_PRE=1 loads sub-chunk 0's
-// with its z in the prologue, =2 also the next sub-chunk's during the current
-// one (phase (5), written in (6)): 31.5 us without, 33.9 us with both
-#ifndef AMH_F64_PRE
-#define AMH_F64_PRE 0
-#endif
-constexpr bool kF64Pre0 = AMH_F64_PRE >= 1;
-constexpr bool kF64Pre = AMH_F64_PRE >= 2;
+// 6: the buffer_inv removed).
 
 namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -142,9 +123,9 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
   constexpr int kSub = kFChunk / kFSub;  // sub-chunks per chunk
   const int64_t Vt = d + 3 * 1024 + 4;   // pooled_big_tile_V(64)
   float* Zs = lds + f64::Z_;
-  // the noise / delta tile and the proposal tile swap roles every sub-chunk:
-  // sub-chunk t + 1's noise is written into this sub-chunk's proposal tile
-  // during phase (6), once phase (5) has read it
+  // the noise / delta tile and the proposal tile swap roles every step: the
+  // next step's noise is written into this step's proposal tile (free once
+  // phase (5) has read it) while phase (6) still reads the delta tile
   float* const XA = lds + f64::XI;
   float* const XB = lds + f64::XP;
   float* Xi = XA;
@@ -211,9 +192,8 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
   int cnt = 0;
   // ---- (1) noise of chains w + 4 N of sub-chunk t: drawn ahead by the
   // previous update launch when the chain's record is this draw's (i, key),
-  // else here.  PRE: the rows are already in xr0 (sub-chunk 0: the prologue)
-  float xr0[16];
-  auto noise_phase = [&](const PooledStatsParams& p, int64_t c0, auto PRE, int32_t its, uint32_t krv, bool records) {
+  // else here
+  auto noise_phase = [&](const PooledStatsParams& p, int64_t c0, int32_t its, uint32_t krv, bool records) {
     uint64_t usem = 0;
     if (ahead && records) {
       // lane N < 16: key word 0 of chain N is its own krv, word 1 lane N + 16's
@@ -232,13 +212,7 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
       const int64_t nrow = p.C - cw;
       const int64_t nr = nrow < 64 ? (nrow > 0 ? nrow : 0) : 64;
       const Buf xb(uniform_ptr(p.xi + cw * d), (uint32_t)(nr * d) * 4u);
-      static_for<16>([&](auto N) {
-        if constexpr (decltype(PRE)::value) {
-          xr[N] = xr0[N];
-        } else {
-          xr[N] = xb.ld(4u * (uint32_t)lane, 4u * (uint32_t)(4 * (int)N * d));
-        }
-      });
+      static_for<16>([&](auto N) { xr[N] = xb.ld(4u * (uint32_t)lane, 4u * (uint32_t)(4 * (int)N * d)); });
       static_for<16>([&](auto N) {
         const int cc = w + 4 * N;
         Xi[cc * kFS + fperm(lane)] = xr[N];
@@ -274,18 +248,11 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
       }
     }
   };
-  // the first sub-chunk's loads -- z, keys, records, pe and (speculatively)
-  // its noise rows -- go out before the shared operands' (one memory latency
-  // in the prologue instead of three)
+  // the first sub-chunk's loads -- z, keys, records and pe -- go out before
+  // the shared operands' (the prologue pays their memory latencies together)
   if (nmine > 0) {
     load_sub(p, 0);
     load_pe(p, 0);
-    const int64_t c00 = sub_c0(0);
-    if constexpr (kF64Pre0) static_for<16>([&](auto N) {
-      int64_t ch = c00 + w + 4 * N;
-      if (ch >= p.C) ch = p.C - 1;
-      xr0[N] = (ahead && ch < p.xi_cap) ? p.xi[ch * d + lane] : 0.0f;
-    });
   }
   // A operands in registers: lane (i, h) of MFMA m holds row 32 T + i, column 2 m + h
   {
@@ -312,12 +279,10 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
   }
   if (nmine > 0) {
     store_z();
-    if constexpr (kF64Pre0) noise_phase(p, sub_c0(0), std::true_type{}, it, kr, true);  // sub-chunk 0's phase (1), its rows already loaded
-    else noise_phase(p, sub_c0(0), std::false_type{}, it, kr, true);
+    noise_phase(p, sub_c0(0), it, kr, true);  // sub-chunk 0's phase (1)
   }
   lds_barrier();
   FS(14)
-  bool pre_ok = false;  // this sub-chunk's noise rows were written during the previous one
   // A pooled block of K steps (sync_every = K) runs in this one launch: a
   // sub-chunk's chains take their K transitions back to back (z in LDS, pe
   // in wave 0's registers between them) before the next sub-chunk, and the
@@ -345,7 +310,8 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
     Xi = (q & 1) ? XB : XA;
     Xp = (q & 1) ? XA : XB;
     // (records are for step 0: the update launch draws the next block's first step)
-    if ((t > 0 || s > 0) && !pre_ok) noise_phase(p, c0, std::false_type{}, it + s, kr, s == 0);
+    const bool first = t == 0 && s == 0;  // its noise was drawn before the loop
+    if (!first) noise_phase(p, c0, it + s, kr, s == 0);
     if (fin && more) load_sub(p, t + 1);  // in flight through phases (2) .. (6) of the last step
     FS(0)
     lds_barrier();
@@ -419,21 +385,6 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
     FS(6)
     lds_barrier();
     FS(7)
-    // ---- the next sub-chunk's noise rows, loaded now (its records came with
-    // load_sub(t + 1) in phase (1)) and written to its tile in phase (6)
-    float xn[16];
-    bool pre_next = false;
-    if (kF64Pre && K == 1 && more && ahead) {
-      const int64_t c1 = sub_c0(t + 1);
-      static_for<16>([&](auto N) {
-        int64_t ch = c1 + w + 4 * N;
-        if (ch >= p.C) ch = p.C - 1;
-        xn[N] = (ch < p.xi_cap) ? p.xi[ch * d + lane] : 0.0f;
-      });
-      const uint32_t kw1 = (uint32_t)__shfl_down((int)kr, 16, 64);
-      const bool ok = (lane < 16) && rec.x == (uint32_t)it && rec.y == kr && rec.z == kw1;
-      pre_next = __ballot(ok) == 0xFFFFull;
-    }
     // ---- (5) z' out, delta = z' - mu as [k][fperm chain] over the xi array
     //      (every LDS read first, then the stores)
     {
@@ -469,15 +420,6 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
     FS(8)
     lds_barrier();
     FS(9)
-    if (pre_next) {  // the proposal tile is free now: sub-chunk t + 1's noise and u
-      static_for<16>([&](auto N) {
-        const int cc = w + 4 * N;
-        Xp[cc * kFS + fperm(lane)] = xn[N];
-        const uint32_t ub = (uint32_t)__builtin_amdgcn_readlane((int)rec.w, N);
-        if (lane == 0) uu[cc] = amh_unif01_from_bits(ub);
-      });
-    }
-    pre_ok = pre_next;
     // ---- (6) the chunk's sums, accumulated over its sub-chunks in chain order
     {
       const bool last = fin && ((t % kSub == kSub - 1) || !more);  // the chunk's last sub-chunk, last step
@@ -708,21 +650,14 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
             });
           } else {
           const uint32_t kk0 = p.keys[2 * ch], kk1 = p.keys[2 * ch + 1];
-#ifndef AMH_FB_NORNG
           float xr[NQ];
           uint32_t ubw;
           step_noise_rows<NQ>(lane, D, (uint32_t)it, kk0, kk1, xr, &ubw);  // bit spec: amh_step_word
-#endif
           static_for<NQ>([&](auto Q) {
             const int k = 64 * Q + lane;
             if (k < D) {
-#ifndef AMH_FB_NORNG
               Xb[k * kLd + cc] = xr[Q];
               if (k == 0) uu[cc] = amh_unif01_from_bits(ubw);
-#else
-              Xb[k * kLd + cc] = (float)((kk0 + k) & 15) * 0.1f - 0.75f;
-              if (k == 0) uu[cc] = 0.5f;
-#endif
               Zb[k * kLd + cc] = zv[N][Q];
             }
           });
@@ -740,7 +675,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
           const int T = pT;
           f32x16 acc0 = f32x16{}, acc1 = f32x16{};
           const f32x4* a = LP + (T * (T + 1) / 2) * 256 + lane;
-#ifndef AMH_FB_NOPROP
           // the next A tile is prefetched unconditionally (a conditional load
           // is sunk next to its use); the B operands of a tile are read in
           // one batch ahead of its MFMAs
@@ -769,7 +703,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
             __builtin_amdgcn_sched_barrier(0);  // the hand-over stays behind the MFMAs
             static_for<4>([&](auto KB) { cur[KB] = nxt[KB]; });
           }
-#endif
           static_for<16>([&](auto R) {
             const int rr = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
             v0[R] = fmaf(el, acc0[(int)R], p.eps * Xb[rr * kLd + i]);
@@ -797,7 +730,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
         const int T = qT;
         f32x16 acc0 = f32x16{}, acc1 = f32x16{};
         const f32x4* a = PP + (T * NT) * 256 + lane;
-#ifndef AMH_FB_NOPOT
         auto tile = [&](const f32x4 (&at)[4], int J) {
           const float* zb = Zb + (32 * J + h) * kLd + i;
           float b0[16], b1[16];
@@ -823,7 +755,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
           __builtin_amdgcn_sched_barrier(0);  // the hand-over stays behind the MFMAs
           static_for<4>([&](auto KB) { cur[KB] = nxt[KB]; });
         }
-#endif
         float ps0 = 0.0f, ps1 = 0.0f;
         static_for<16>([&](auto R) {
           const int row = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
@@ -920,7 +851,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
           static_for<16>([&](auto R) { sacc[S][(int)R] = o[64 * R]; });
         }
       });
-#ifndef AMH_FB_NOSDD
       {
         // all of the wave's tile pairs per 8-chain block: the block's
         // operands read in one LDS batch, then the pairs' MFMAs interleaved
@@ -955,7 +885,6 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
               sacc[S] = __builtin_amdgcn_mfma_f32_32x32x2f32(Zb[ra[S] + kk + h], Zb[rb[S] + kk + h], sacc[S], 0, 0, 0);
           });
       }
-#endif
       // S_dd tiles in register order: one coalesced 256-B row per register
       // (the final values after the chunk's last half)
       static_for<NS>([&](auto S) {
@@ -1044,10 +973,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // 16 waves (115 VGPRs with d a compile-time constant; 8 waves measured
 // 2 % slower at d = 256)
-#ifndef AMH_UPD_WAVES
-#define AMH_UPD_WAVES 16
-#endif
-constexpr int kUpdWaves = AMH_UPD_WAVES;
+constexpr int kUpdWaves = 16;
 
 // Trailing update of one 32x32 tile (I >= J, in 32-row blocks of the
 // trailing matrix that starts at row / column q0) by the panel of columns
@@ -1658,17 +1584,15 @@ __global__ __launch_bounds__(512) void pooled_update64_kernel(PooledUpdateParams
     URT_MAX(1, URT_NOW())
     __shared__ int tk;
     int* ticket = (int*)p.scratch + d * (d + 4) / 2 + 5;
-    // a relaxed ticket after the write-through stores completed; the last
-    // arriver acquires (AMH_TICKET_ORDER above)
-    if (threadIdx.x == 0) tk = __hip_atomic_fetch_add(ticket, 1, AMH_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+    // a relaxed ticket after the write-through stores completed (the
+    // hand-off comment at the top of this file)
+    if (threadIdx.x == 0) tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     // The last arriver reads every block's sums with sc1 (agent-scope relaxed)
     // loads only, the producers stored them sc1 and drained before their add:
     // the write-through form that replaces the acquire (MI355X_MICROARCH.md,
     // inter-workgroup visibility, "Valid forms", first table row), so no
     // buffer_inv (~1.7 us) sits on the update's critical path.
-    // AMH_HANDOFF_FENCE=1 keeps the acquire (A/B).
-    if (AMH_HANDOFF_FENCE && tk == nred - 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (tk != nred - 1) {  // not the last: a noise worker
       if (nlate == 0) {
         URT_FLUSH
@@ -2022,8 +1946,9 @@ __global__ __launch_bounds__(256) void pooled_big_post_kernel(PooledUpdateParams
   __syncthreads();
   // the column sum goes out write-through (sc1) and the block takes a ticket;
   // the block that takes the last one sums the columns (cross-XCD hand-off:
-  // sc1 stores, vmcnt(0), relaxed agent-scope add, acquire + sc1 loads by the
-  // last arriver -- cdna_hip_programming.md's write-through counter recipe)
+  // sc1 stores, vmcnt(0), relaxed agent-scope add, sc1 loads by the last
+  // arriver and no acquire fence, as in update64 -- cdna_hip_programming.md's
+  // write-through counter recipe)
   uint32_t* colsum = (uint32_t*)(p.scratch + nA + 8);
   int* ticket = (int*)p.scratch + nA + 5;
   __shared__ int last;
@@ -2031,11 +1956,10 @@ __global__ __launch_bounds__(256) void pooled_big_post_kernel(PooledUpdateParams
     const float cs = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
     __hip_atomic_store(&colsum[k], __float_as_uint(cs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = __hip_atomic_fetch_add(ticket, 1, AMH_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == d - 1;
+    last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == d - 1;
   }
   __syncthreads();
   if (!last) return;
-  if (AMH_HANDOFF_FENCE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // sc1 loads below (see update64)
   // as_change = sqrtf(big_sum of the column sums)
   const float v = t < d ? __uint_as_float(__hip_atomic_load(&colsum[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
                         : 0.0f;

@@ -211,19 +211,8 @@ __device__ __forceinline__ void step_noise(int r, int d, uint32_t it, uint32_t k
 // fourth copy of call 15 and takes its own word (word 3 of call 15) from lane
 // 60 -- two v_readlane and two selects instead of a second Philox call (the
 // round-5 form ran call 16 on the scalar unit: ~60 more instructions per
-// chain-step, AMH_S64_NOISE_SCALAR=1 keeps it for A/B).  The same bits as
-// step_noise<64>.
+// chain-step).  The same bits as step_noise<64>.
 __device__ __forceinline__ void step_noise_w64(int r, uint32_t it, uint32_t k0, uint32_t k1, float& xi, float& u) {
-#if AMH_S64_NOISE_SCALAR
-  const amh_u32x4 o = amh_philox4x32_10((uint32_t)(r >> 2), it, 0u, AMH_TAG_STEP, k0, k1);
-  const int q = r & 3;
-  const uint32_t w = (q == 0) ? o.v[0] : ((q == 1) ? o.v[1] : ((q == 2) ? o.v[2] : o.v[3]));
-  xi = amh_normal_from_bits(w);
-  const uint32_t ks0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0);
-  const uint32_t ks1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k1);
-  const uint32_t its = (uint32_t)__builtin_amdgcn_readfirstlane((int)it);
-  u = amh_unif01_from_bits(amh_philox4x32_10(16u, its, 0u, AMH_TAG_STEP, ks0, ks1).v[0]);
-#else
   const bool l63 = (r == 63);
   const amh_u32x4 o = amh_philox4x32_10(l63 ? 16u : (uint32_t)(r >> 2), it, 0u, AMH_TAG_STEP, k0, k1);
   const int q = r & 3;
@@ -232,7 +221,6 @@ __device__ __forceinline__ void step_noise_w64(int r, uint32_t it, uint32_t k0, 
   const uint32_t ub = (uint32_t)__builtin_amdgcn_readlane((int)o.v[0], 63);   // word 64
   xi = amh_normal_from_bits(l63 ? w63 : w);
   u = amh_unif01_from_bits(ub);
-#endif
 }
 
 // The same stream for one chain per wave with lane l owning rows 64 K + l
@@ -757,9 +745,6 @@ struct is_external<T, std::void_t<decltype(T::kExternal)>> : std::bool_constant<
 // --------------------------------------------------------------- geometry --
 constexpr int kBlock = 256;       // 4 waves (init / potential / sample_Pnx kernels)
 constexpr int kBlockStep = 1024;  // 16 waves per CU share one staged copy of the model data
-#ifndef AMH_STEP_MIN_WAVES
-#define AMH_STEP_MIN_WAVES 1  // waves per SIMD the step kernel must fit (VGPR budget)
-#endif
 
 template <int G>
 struct Geo {
@@ -808,12 +793,8 @@ __device__ __forceinline__ float lookup_gamma(const StepParams& p, int32_t n) {
 // that must not touch memory get an out-of-range voffset (loads return 0,
 // stores are dropped by the hardware range check).
 constexpr uint32_t kOOB = 0x80000000u;
-#ifndef AMH_STORE_AUX
-#define AMH_STORE_AUX 2  // cache policy of state stores: nt (streaming, written once per launch)
-#endif
-#ifndef AMH_LOAD_AUX
-#define AMH_LOAD_AUX 2  // cache policy of the factor's DMA loads: nt (read once per launch)
-#endif
+constexpr int kStoreAux = 2;  // cache policy of state stores: nt (streaming, written once per launch)
+constexpr int kLoadAux = 2;   // cache policy of the factor's DMA loads: nt (read once per launch)
 
 struct Buf {
   __amdgpu_buffer_rsrc_t rs;
@@ -824,7 +805,7 @@ struct Buf {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
   }
   __device__ __forceinline__ void st(float v, uint32_t voff, uint32_t soff) const {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)voff, (int)soff, AMH_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)voff, (int)soff, kStoreAux);
   }
 };
 

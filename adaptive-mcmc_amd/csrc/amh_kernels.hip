@@ -57,10 +57,10 @@ __device__ __forceinline__ void prefetch_item(const StepParams& p, int64_t first
     // DMA inside this wave's buffer (an LDS-DMA writes base + 4*size*lane)
     const uint32_t n16 = vec ? (total / 1024u) * 1024u : 0u;
     for (uint32_t o = 0; o < n16; o += 1024u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 16, (int)(o + 16u * lane), 0, 0, AMH_LOAD_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 16, (int)(o + 16u * lane), 0, 0, kLoadAux);
     for (uint32_t o = n16; o < total; o += 256u) {
       if (o + 4u * lane < total)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 4, (int)(o + 4u * lane), 0, 0, AMH_LOAD_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 4, (int)(o + 4u * lane), 0, 0, kLoadAux);
     }
   }
   {
@@ -834,19 +834,10 @@ __global__ void chain_keys_kernel(uint32_t key0, uint32_t key1, int64_t offset, 
 //   per-wave scratch and read back four columns at a time with broadcast
 //   ds_read_b128, in place of v_readlane + s_nop per column.  Only sweep 1,
 //   whose w_j is serial, still uses v_readlane.
-#ifndef AMH_S64_WAVES
-#define AMH_S64_WAVES 16
-#endif
-constexpr int kS64Waves = AMH_S64_WAVES;
-#ifndef AMH_S64_EB
-#define AMH_S64_EB 8
-#endif
-#ifndef AMH_S64_PB
-#define AMH_S64_PB 8
-#endif
-constexpr int kS64EB = AMH_S64_EB;  // proposal: broadcast columns per LDS wait (16 or 8)
-constexpr int kS64PB = AMH_S64_PB;  // potential: columns per LDS wait (16 or 8)
-static_assert((kS64EB == 16 || kS64EB == 8) && (kS64PB == 16 || kS64PB == 8), "batch sizes");
+constexpr int kS64Waves = 16;
+constexpr int kS64EB = 8;  // proposal: broadcast columns per LDS wait
+constexpr int kS64PB = 8;  // potential: columns per LDS wait
+static_assert(kS64EB == 8 && kS64PB == 8, "the batch readers (lds_ld4x2w / lds_ld4x4w) read two quarter-vectors per stream");
 typedef uint32_t uint32x4_t_ __attribute__((ext_vector_type(4)));
 constexpr int kS64P = 2080;                   // d(d+1)/2
 constexpr int kS64Z = 2080, kS64M = 2144, kS64S = 2208, kS64X = 2216;  // wave-buffer offsets (floats)
@@ -880,26 +871,9 @@ __device__ __forceinline__ void s64_mul_above(float& u, float t, float s) {
   asm volatile("s_mov_b64 %1, exec\n\ts_lshl_b64 exec, -1, %4\n\tv_mul_f32 %0, %2, %3\n\ts_mov_b64 exec, %1"
                : "+v"(u), "=&s"(sv) : "v"(t), "v"(s), "n"(J + 1));
 }
-// sweep 1, column J: w_J broadcast, then w -= w_J U_rJ on lanes r > J.  A VALU
-// read of an SGPR written by v_readlane needs two wait states, and SALU
-// instructions in between do not provide them (measured: with only the exec
-// setup in between, a few chains per thousand read the previous column's
-// w_j), so the s_nop 1 stays.
-template <int J>
-__device__ __forceinline__ void s64_sweep1(float& w, float u) {
-  uint64_t sv;
-  uint32_t t;
-  asm volatile("s_mov_b64 %2, exec\n\ts_lshl_b64 exec, -1, %5\n\tv_readlane_b32 %1, %0, %4\n\ts_nop 1\n\t"
-               "v_fma_f32 %0, -%1, %3, %0\n\ts_mov_b64 exec, %2"
-               : "+v"(w), "=&s"(t), "=&s"(sv) : "v"(u), "n"(J), "n"(J + 1));
-}
 // LDS batches read and waited for in ONE statement (outputs "=&v"): per
-// batch one boundary pad instead of two (the separate read and wait
-// statements each had hipcc's pad around them).  AMH_S64_LDSW=0 keeps the
-// separate statements (A/B).
-#ifndef AMH_S64_LDSW
-#define AMH_S64_LDSW 1
-#endif
+// batch one boundary pad instead of two (separate read and wait statements
+// each have hipcc's pad around them).
 template <int O0, int O1>
 __device__ __forceinline__ void lds_ld4x2w(f32x4& a, f32x4& b, uint32_t addr) {
   asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4\n\ts_waitcnt lgkmcnt(0)"
@@ -915,13 +889,16 @@ __device__ __forceinline__ void lds_ld4x4w(f32x4& a, f32x4& b, f32x4& c, f32x4& 
                : "v"(addr0), "v"(addr1), "n"(O0), "n"(O1), "n"(O2), "n"(O3));
 }
 
-// sweep 1 over eight columns J0 .. J0 + 7 (seven when J0 = 56: columns up to
-// 62) in one statement: exec saved once and restored once, each column
-// s_lshl exec (lanes r > J) / v_readlane / s_nop 1 / v_fma / s_nop 0 -- the
-// s_nop 0 is the VALU-write -> v_readlane wait state of the next column (the
-// per-column statements had hipcc's boundary pad there, plus an exec save
-// and restore per column: 8 slots per column, now 5).  The same fma, in the
-// same order, as s64_sweep1.
+// sweep 1 (column J: w_J broadcast, then w -= w_J U_rJ on lanes r > J) over
+// eight columns J0 .. J0 + 7 (seven when J0 = 56: columns up to 62) in one
+// statement: exec saved once and restored once, each column s_lshl exec
+// (lanes r > J) / v_readlane / s_nop 1 / v_fma / s_nop 0.  A VALU read of an
+// SGPR written by v_readlane needs two wait states, and SALU instructions in
+// between do not provide them (measured: with only the exec setup in
+// between, a few chains per thousand read the previous column's w_j), so the
+// s_nop 1 stays.  The s_nop 0 is the VALU-write -> v_readlane wait state of
+// the next column (one statement per column has hipcc's boundary pad there,
+// plus an exec save and restore per column: 8 slots per column, here 5).
 #define AMH_SW1_COL(k)                                                          \
   "s_lshl_b64 exec, -1, %[s" #k "]\n\tv_readlane_b32 %[t], %[w], %[l" #k "]\n\t" \
   "s_nop 1\n\tv_fma_f32 %[w], -%[t], %[u" #k "], %[w]\n\ts_nop 0\n\t"
@@ -952,22 +929,12 @@ __device__ __forceinline__ void s64_sweep1x8(float& w, const float (&U)[64]) {
   }
 }
 #undef AMH_SW1_COL
-#ifndef AMH_S64_SW1_PERCOL
-#define AMH_S64_SW1_PERCOL 0  // 1: the per-column statements (A/B)
-#endif
 // the whole sweep 1 (columns 0 .. 62)
 __device__ __forceinline__ void s64_sweep1_all(float& w, const float (&U)[64]) {
-#if AMH_S64_SW1_PERCOL
-  static_for<63>([&](auto J) {
-    s64_sweep1<J>(w, U[J]);
-    column_fence<J>();
-  });
-#else
   static_for<8>([&](auto B) {
     s64_sweep1x8<8 * B>(w, U);
     __builtin_amdgcn_sched_barrier(0);
   });
-#endif
 }
 
 // lanes 16Q .. 16Q+15 write v0..v3 at a, a+64, a+128, a+192 (a = scratch + 4 (r mod 16))
@@ -1012,20 +979,7 @@ __device__ __forceinline__ float s64_gauss_pot(float diff, uint32_t x_a, uint32_
     constexpr int b = B;
     constexpr int NQ = kS64PB / 4;
     f32x4 pv[NQ], dv[NQ];
-    if constexpr (NQ == 2 && AMH_S64_LDSW) {
-      lds_ld4x4w<16 * (2 * b), 16 * (2 * b + 1), 16 * (2 * b), 16 * (2 * b + 1)>(pv[0], pv[1], dv[0], dv[1], prow, x_a);
-    } else {
-      static_for<NQ>([&](auto Q) {
-        pv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(prow);
-        dv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(x_a);
-      });
-      if constexpr (NQ == 4) {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(dv[0]),
-                     "+v"(dv[1]), "+v"(dv[2]), "+v"(dv[3]));
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(dv[0]), "+v"(dv[1]));
-      }
-    }
+    lds_ld4x4w<16 * (2 * b), 16 * (2 * b + 1), 16 * (2 * b), 16 * (2 * b + 1)>(pv[0], pv[1], dv[0], dv[1], prow, x_a);
     static_for<2 * NQ>([&](auto K2) {
       const f32x4 q = pv[(int)K2 / 2];
       const f32x4 dq = dv[(int)K2 / 2];
@@ -1049,7 +1003,7 @@ __device__ __forceinline__ float s64_gauss_pot(float diff, uint32_t x_a, uint32_
 // the same bits as the generic transition and orc_asss_step), with the
 // column broadcasts of the step64 ARWMH path -- the matrix-vector products
 // S z, S v and every potential read their broadcast vector from the wave's
-// LDS scratch, sweep 1 is s64_sweep1, sweep 2 the quarter-vector LDS scheme,
+// LDS scratch, sweep 1 is s64_sweep1_all, sweep 2 the quarter-vector LDS scheme,
 // and the forward solve keeps one v_readlane per column (its own y_j by a
 // select).  The generic form spent ~576 + 64 (shrink steps + 2) v_readlane per
 // transition.
@@ -1107,16 +1061,7 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
     static_for<d / kS64EB>([&](auto B) {
       constexpr int bb = B;
       f32x4 ev[kS64EB / 4];
-      if constexpr (kS64EB == 8 && AMH_S64_LDSW) {
-        lds_ld4x2w<16 * (2 * bb), 16 * (2 * bb + 1)>(ev[0], ev[1], x_a);
-      } else {
-        static_for<kS64EB / 4>([&](auto Q) { ev[(int)Q] = lds_ld4<16 * (kS64EB / 4 * bb + Q)>(x_a); });
-        if constexpr (kS64EB == 16) {
-          lds_wait(ev[0], ev[1], ev[2], ev[3]);
-        } else {
-          s64_tie(ev[0], ev[1]);
-        }
-      }
+      lds_ld4x2w<16 * (2 * bb), 16 * (2 * bb + 1)>(ev[0], ev[1], x_a);
       static_for<kS64EB>([&](auto K) {
         constexpr int j = kS64EB * bb + K;
         a4[j & 3] = fmaf(U[j], ev[(int)K / 4][(int)K % 4], a4[j & 3]);
@@ -1219,13 +1164,7 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
       if constexpr (g % 4 == 0) s64_wr4_quarter<g / 4>(xq_a, ws, cc, ac, bc);
       constexpr int gq = g % 4;
       f32x4 cw, cv, ca, cb;
-#if AMH_S64_LDSW
       lds_ld4x4w<16 * gq, 64 + 16 * gq, 128 + 16 * gq, 192 + 16 * gq>(cw, cv, ca, cb, x_a, x_a);
-#else
-      cw = lds_ld4<16 * gq>(x_a), cv = lds_ld4<64 + 16 * gq>(x_a);
-      ca = lds_ld4<128 + 16 * gq>(x_a), cb = lds_ld4<192 + 16 * gq>(x_a);
-      lds_wait(cw, cv, ca, cb);
-#endif
       static_for<4>([&](auto Q) {
         constexpr int j = 4 * g + Q;
         const float uo = U[j];
@@ -1348,7 +1287,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       static_for<3>([&](auto Q) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint32x4_t_, v[(int)Q]), Lout.rs,
                                                (int)(1024u * (3 * G + Q) + 16u * (uint32_t)lane_id()), 0,
-                                               AMH_STORE_AUX);
+                                               kStoreAux);
       });
     });
   };
@@ -1434,11 +1373,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     bool updated = false;
     for (int32_t t = 0; t < p.n_steps; ++t) {
      if constexpr (kASSS) {
-#if AMH_S64_ASSS_GENERIC
-      asss_transition<64, GaussianM, true>(p, U, dl, z, mu, pe, asc, updated, it, k0, k1, D, r, r, true, mctx, lds);
-#else
       asss_transition64(p, U, dl, z, mu, pe, asc, updated, it, k0, k1, r, mctx, x_a, xq_a, prow);
-#endif
       it += 1;
      } else {
       // ---- noise (arwmh.py:162-165, 174): stream position = state.i
@@ -1453,16 +1388,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       static_for<D / kS64EB>([&](auto B) {  // kS64EB columns per batch
         constexpr int b = B;
         f32x4 e[kS64EB / 4];
-        if constexpr (kS64EB == 8 && AMH_S64_LDSW) {
-          lds_ld4x2w<16 * (2 * b), 16 * (2 * b + 1)>(e[0], e[1], x_a);
-        } else {
-          static_for<kS64EB / 4>([&](auto Q) { e[(int)Q] = lds_ld4<16 * (kS64EB / 4 * b + Q)>(x_a); });
-          if constexpr (kS64EB == 16) {
-            lds_wait(e[0], e[1], e[2], e[3]);
-          } else {
-            s64_tie(e[0], e[1]);
-          }
-        }
+        lds_ld4x2w<16 * (2 * b), 16 * (2 * b + 1)>(e[0], e[1], x_a);
         static_for<kS64EB>([&](auto K) {
           constexpr int j = kS64EB * b + K;
           a4[j & 3] = fmaf(U[j], e[(int)K / 4][(int)K % 4], a4[j & 3]);
@@ -1482,20 +1408,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
           constexpr int b = B;
           constexpr int NQ = kS64PB / 4;
           f32x4 pv[NQ], dv[NQ];
-          if constexpr (NQ == 2 && AMH_S64_LDSW) {
-            lds_ld4x4w<16 * (2 * b), 16 * (2 * b + 1), 16 * (2 * b), 16 * (2 * b + 1)>(pv[0], pv[1], dv[0], dv[1], prow, x_a);
-          } else {
-            static_for<NQ>([&](auto Q) {
-              pv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(prow);
-              dv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(x_a);
-            });
-            if constexpr (NQ == 4) {
-              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(dv[0]),
-                           "+v"(dv[1]), "+v"(dv[2]), "+v"(dv[3]));
-            } else {
-              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(dv[0]), "+v"(dv[1]));
-            }
-          }
+          lds_ld4x4w<16 * (2 * b), 16 * (2 * b + 1), 16 * (2 * b), 16 * (2 * b + 1)>(pv[0], pv[1], dv[0], dv[1], prow, x_a);
           static_for<2 * NQ>([&](auto K2) {
             const f32x4 q = pv[(int)K2 / 2];
             const f32x4 dq = dv[(int)K2 / 2];
@@ -1567,13 +1480,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
           if constexpr (g % 4 == 0) s64_wr4_quarter<g / 4>(xq_a, ws, c, ac, bc);
           constexpr int gq = g % 4;
           f32x4 cw, cc, ca, cb;
-#if AMH_S64_LDSW
           lds_ld4x4w<16 * gq, 64 + 16 * gq, 128 + 16 * gq, 192 + 16 * gq>(cw, cc, ca, cb, x_a, x_a);
-#else
-          cw = lds_ld4<16 * gq>(x_a), cc = lds_ld4<64 + 16 * gq>(x_a);
-          ca = lds_ld4<128 + 16 * gq>(x_a), cb = lds_ld4<192 + 16 * gq>(x_a);
-          lds_wait(cw, cc, ca, cb);
-#endif
           static_for<4>([&](auto Q) {
             constexpr int j = 4 * g + Q;
             const float uo = U[j];
@@ -1870,13 +1777,11 @@ hipError_t run_step(int model_id, const StepParams& p, hipStream_t s) {
 }
 // ASSS at the d = 64 Gaussian (amh_asss.hip run_asss_step): the persistent
 // LDS-staged kernel around the ASSS transition
-#ifndef AMH_ASSS64_WAVES
 // 16 waves (128 VGPRs, 64 B of spill) measured 0.343 ms per sample() against
 // 0.363 ms at 12 waves (170 VGPRs, no spill): the occupancy pays for the spill
-#define AMH_ASSS64_WAVES 16
-#endif
+constexpr int kAsss64Waves = 16;
 hipError_t run_asss_step64(const StepParams& p, hipStream_t s) {
-  return launch_step64<AMH_ASSS64_WAVES, true>(p, s);
+  return launch_step64<kAsss64Waves, true>(p, s);
 }
 
 hipError_t run_init(int model_id, const InitParams& p, hipStream_t s) {

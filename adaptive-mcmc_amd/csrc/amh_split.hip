@@ -337,14 +337,9 @@ __global__ __launch_bounds__(256, (NB == 2 ? 2 : 1)) void diamonds_pot_mfma_kern
     static_for<G>([&](auto Q) { a[Q] = an[Q]; });
     static_for<4>([&](auto Q) { y[Q] = yn[Q]; });
   };
-#ifdef AMH_DIA_SELECT_ALL
-#pragma unroll 1
-  for (int64_t m = 0; m < NT; ++m) tile(m, std::false_type{});
-#else
 #pragma unroll 1
   for (int64_t m = 0; m + 1 < NT; ++m) tile(m, std::true_type{});
   if (NT > 0) tile(NT - 1, std::false_type{});
-#endif
   // chain pair (2P, 2P + 1): lane (i, 0) finishes chain 2P, lane (i, 1) chain
   // 2P + 1; the other half's residues arrive by a 32-lane swap
   static_for<NB / 2>([&](auto PP) {

@@ -1,12 +1,14 @@
 #!/bin/bash
 # diagnostic builds of libamh.so with compile-time switches of one source
 # file: tools/build_variants.sh SRC "name:-DFLAG ..." ... -> lib/var_<name>/libamh.so
-# (select one at run time with AMH_LIB_PATH)
+# (select one at run time with AMH_LIB_PATH).  The compile flags are the
+# Makefile's (its `flags` target), so a variant differs from the release
+# build by its own defines only.
 set -e
 cd "$(dirname "$0")/../adaptive-mcmc_amd/csrc"
 SRC=$1; shift
 OUT=../lib
-FLAGS="--offload-arch=gfx950 -O3 -std=c++20 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -munsafe-fp-atomics -mllvm -amdgpu-atomic-optimizer-strategy=None"
+FLAGS=$(make -s --no-print-directory flags)
 base=$(basename $SRC .hip)
 for v in "$@"; do
   name=${v%%:*}; defs=${v#*:}

@@ -5,7 +5,7 @@
 // Each kernel moves exactly BYTES (1 GiB, four times the 256 MiB Infinity
 // Cache) once:
 //   rd_lds16_aux<A>   buffer_load ... lds, 16 B/lane (the factor's DMA loads),
-//                     cache policy A (0 = default, 2 = nt as AMH_LOAD_AUX)
+//                     cache policy A (0 = default, 2 = nt as kLoadAux of amh_device.h)
 //   rd_lds4           buffer_load ... lds, 4 B/lane, default policy (z, loc)
 //   rd_global16       plain global_load_dwordx4 (the guide's reference case)
 //   wr_b32_aux<A>     buffer_store_dword, 4 B/lane, policy A (state stores)
