@@ -450,7 +450,7 @@ struct EightSchoolsM {
       v = ((-0.5f * (t * t)) - 1.60943791243410037f) - HALF_LOG_2PI;
     } else if (r == 1) {
       const float t = tau / 5.0f;
-      v = ((-0.451582705289454865f - 1.60943791243410037f) - amh_log1pf(t * t)) + lt;
+      v = ((-0.451582705289454865f - 1.60943791243410037f) - amh_log1p_sqf(t)) + lt;
     } else if (r < d) {
       const float th = x;
       const float lpt = (-0.5f * (th * th)) - HALF_LOG_2PI;
@@ -494,14 +494,14 @@ struct KidiqM {
     const float S = Grp<G>::sum(acc);
     const float t = sg / 2.5f;
     const float ll = fmaf(-0.5f, S, (float)N * ((-ls) - HALF_LOG_2PI));
-    const float lpr = ((-0.451582705289454865f - 0.916290731874155065f) - amh_log1pf(t * t)) + ls;
+    const float lpr = ((-0.451582705289454865f - 0.916290731874155065f) - amh_log1p_sqf(t)) + ls;
     return -(ll + lpr);
   }
 };
 
 __device__ __forceinline__ float lp_student3(float x, float loc, float scale, float c) {
   const float t = (x - loc) / scale;
-  return c - 2.0f * amh_log1pf((t * t) / 3.0f);
+  return c - 2.0f * amh_log1p_sq3f(t);
 }
 
 template <int G>

@@ -9,9 +9,11 @@
  * transcendental is called, because those differ between host and device.
  * Both sides are compiled with -ffp-contract=off so nothing else fuses.
  *
- * The functions are pinned independently of this file by tests/test_math.py
- * (numpy/scipy float64 references) and tests/test_rng.py (Random123 KAT
- * vectors for Philox4x32-10).
+ * The functions are pinned independently of this file by
+ * tests/test_rng_math.py (the host compile: numpy/scipy float64 references and
+ * Random123 KAT vectors for Philox4x32-10) and, for the device compile, by
+ * tests/test_gpu_eval.py::test_normals_bitexact (amh_normals against the host
+ * compile, bit for bit: Philox, amh_logf, sqrtf and both erfinv polynomials).
  *
  * Reference anchors (what the noise stands in for):
  *   arwmh.py:162  rng_key, key_proposal, key_accept = random.split(rng_key, 3)
@@ -199,6 +201,24 @@ AMH_HD float amh_log1pf(float x) {
   if (u == 1.0f) return x;
   if (u == INFINITY) return u;
   return amh_logf(u) * (x / (u - 1.0f));
+}
+
+/* log1p(t^2) and log1p(t^2 / 3) (the half-Cauchy and Student-t(3) priors of
+ * a scale sigma = e^ls) without the float32 overflow of the square: past
+ * |t| = 1.8e19 (t^2 >= 3.2e38) the result is 2 log|t| (- log 3) to far below
+ * an ulp, where t * t would be +inf and the potential of a finite point
+ * non-finite (a log-scale coordinate between 45 and 88; tests/test_edges.py
+ * test_potential_anchor).  Below the threshold the value is the plain form's,
+ * bit for bit. */
+AMH_HD float amh_log1p_sqf(float t) {
+  const float a = fabsf(t);
+  if (a > 1.8e19f && a < INFINITY) return 2.0f * amh_logf(a);
+  return amh_log1pf(t * t);
+}
+AMH_HD float amh_log1p_sq3f(float t) {
+  const float a = fabsf(t);
+  if (a > 1.8e19f && a < INFINITY) return fmaf(2.0f, amh_logf(a), -1.09861228866810969f);
+  return amh_log1pf((t * t) / 3.0f);
 }
 
 /* ------------------------------------------------------------- erfinv ---- */

@@ -140,7 +140,7 @@ static float pot_eight_schools(const orc_cfg* cfg, const float* x, int G) {
     } else if (r == 1) {
       const float t = tau / 5.0f;
       /* log HalfCauchy(tau; 5) + log|d tau / d lt| */
-      v = ((-0.451582705289454865f - 1.60943791243410037f) - amh_log1pf(t * t)) + lt;
+      v = ((-0.451582705289454865f - 1.60943791243410037f) - amh_log1p_sqf(t)) + lt;
     } else if (r < d) {
       const int j = r - 2;
       const float th = x[r];
@@ -179,7 +179,7 @@ static float pot_kidiq(const orc_cfg* cfg, const float* x, int G) {
   const float t = sg / 2.5f;
   /* -[ N*(-log sigma - HALF_LOG_2PI) - S/2 + logHalfCauchy(sigma;2.5) + ls ] */
   const float ll = fmaf(-0.5f, S, (float)N * ((-ls) - HALF_LOG_2PI));
-  const float lpr = ((-0.451582705289454865f - 0.916290731874155065f) - amh_log1pf(t * t)) + ls;
+  const float lpr = ((-0.451582705289454865f - 0.916290731874155065f) - amh_log1p_sqf(t)) + ls;
   return -(ll + lpr);
 }
 
@@ -187,7 +187,7 @@ static float pot_kidiq(const orc_cfg* cfg, const float* x, int G) {
  * folded into c (= lgamma(2) - lgamma(1.5) - 0.5 log(3 pi) - log scale). */
 static float lp_student3(float x, float loc, float scale, float c) {
   const float t = (x - loc) / scale;
-  return c - 2.0f * amh_log1pf((t * t) / 3.0f);
+  return c - 2.0f * amh_log1p_sq3f(t);
 }
 
 /* diamonds (run_diamonds_lr_decay.py:24-40).

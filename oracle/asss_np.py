@@ -2,8 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY (never imported by the product package).
 
-Follows python/kernels/asss.py statement by statement at float64 (or a
-selected dtype), with the random draws injected so the bit-level C oracle
+Follows python/kernels/asss.py statement by statement at float64 or at a
+selected dtype (float32, the reference's own: every statement of the sphere
+map, the shrinkage and the adaptation is then evaluated in it; the potential
+is the caller's float64 function of the float32 point, rounded once), with the random draws injected so the bit-level C oracle
 (oracle/amh_oracle.c, orc_asss_step) and the HIP kernel (amh_asss.hip) can
 be fed the same noise:
 
@@ -29,16 +31,18 @@ MAX_ITERATIONS = 50
 
 
 def stereographic_project(x, loc, scale):
-    """asss.py:33-45 (scale lower triangular)."""
+    """asss.py:33-45 (scale lower triangular); in the dtype of its inputs."""
     from scipy.linalg import solve_triangular
-    xr = solve_triangular(scale, x - loc, lower=True)
+    dt = np.result_type(x, loc, scale)
+    one = dt.type(1)
+    xr = solve_triangular(scale, x - loc, lower=True).astype(dt)
     ns = np.sum(xr ** 2)
-    return np.concatenate([2 * xr / (ns + 1), [(ns - 1) / (ns + 1)]])
+    return np.concatenate([dt.type(2) * xr / (ns + one), [(ns - one) / (ns + one)]]).astype(dt)
 
 
 def stereographic_inverse(z, loc, scale):
     """asss.py:48-56."""
-    x_base = z[:-1] / (1 - z[-1])
+    x_base = z[:-1] / (z.dtype.type(1) - z[-1])
     return scale @ x_base + loc
 
 
@@ -55,24 +59,29 @@ def draws(key, it, d):
 
 
 def shrinkage(z, v, t_pe, transformed_pe_fn, th0, uks, eps=1e-6):
-    """asss.py:59-96 with the initial angle th0 and the loop's uniforms uks."""
-    theta = th0
-    theta_min, theta_max = theta - 2 * np.pi, theta
+    """asss.py:59-96 with the initial angle th0 and the loop's uniforms uks;
+    in the dtype of z (angles, the point on the circle, the slice test)."""
+    T = z.dtype.type
+    theta = T(th0)
+    theta_min, theta_max = theta - T(2 * np.pi), theta
     it = 0
 
+    def at(theta):
+        return z * np.cos(theta) + v * np.sin(theta)
+
     def cond(theta, it):
-        zt = z * np.cos(theta) + v * np.sin(theta)
+        zt = at(theta)
         pe = transformed_pe_fn(zt)
-        pe = np.inf if np.isnan(pe) else pe
-        return it < MAX_ITERATIONS and (pe > t_pe or (1.0 - zt[-1]) < eps)
+        pe = T(np.inf) if np.isnan(pe) else pe
+        return it < MAX_ITERATIONS and (pe > t_pe or (T(1) - zt[-1]) < T(eps))
 
     while cond(theta, it):
-        theta_min = theta if theta < 0.0 else theta_min
-        theta_max = theta if theta >= 0.0 else theta_max
-        theta = theta_min + (theta_max - theta_min) * uks[it]
+        theta_min = theta if theta < 0 else theta_min
+        theta_max = theta if theta >= 0 else theta_max
+        theta = theta_min + (theta_max - theta_min) * T(uks[it])
         it += 1
-    theta = 0.0 if it >= MAX_ITERATIONS else theta
-    return z * np.cos(theta) + v * np.sin(theta), it
+    theta = T(0) if it >= MAX_ITERATIONS else theta
+    return at(theta), it
 
 
 def sample(state: ASSSState, potential_fn, v, u_t, th0, uks, num_warmup=0, lr_decay=2 / 3, eps=1e-6,
@@ -82,29 +91,33 @@ def sample(state: ASSSState, potential_fn, v, u_t, th0, uks, num_warmup=0, lr_de
     loc, scale = (np.asarray(a, dtype) for a in adapt)
     x = np.asarray(x, dtype)
     dim = loc.shape[-1]
+    T = dtype
     with np.errstate(all="ignore"):
-        sigma_sqrt = (scale + eps * np.eye(dim)) * dim ** 0.5
+        sigma_sqrt = (scale + T(eps) * np.eye(dim, dtype=dtype)) * np.sqrt(T(dim))
+
+        def pot(xf):  # the potential of a point held in dtype, returned in dtype
+            return T(potential_fn(xf))
 
         def transformed_pe(z):
             xf = stereographic_inverse(z, loc, sigma_sqrt)
-            return potential_fn(xf) + dim * np.log(1.0 - z[-1])
+            return pot(xf) + T(dim) * np.log(T(1) - z[-1])
 
         z = stereographic_project(x, loc, sigma_sqrt)
         pe_t = transformed_pe(z)
         v = np.asarray(v, dtype)
         v = v - np.dot(v, z) * z
         v = v / np.linalg.norm(v)
-        t_pe = pe_t - np.log(u_t)
+        t_pe = pe_t - np.log(T(u_t))
         z_new, n_iter = shrinkage(z, v, t_pe, transformed_pe, th0, uks, eps)
         x_new = stereographic_inverse(z_new, loc, sigma_sqrt)
-        pe_new = potential_fn(x_new)
-        pe_new = np.inf if np.isnan(pe_new) else pe_new
+        pe_new = pot(x_new)
+        pe_new = T(np.inf) if np.isnan(pe_new) else pe_new
         itr = int(i) + 1
         n = itr if int(i) < num_warmup else itr - num_warmup
         gamma = lr_gamma(n, lr_decay, dtype)
         delta = x_new - loc
         loc_new = loc + gamma * delta
-        chol = cholesky_update(np.sqrt(1 - gamma) * scale, delta, gamma, dtype)
+        chol = cholesky_update(np.sqrt(T(1) - gamma) * scale, delta, gamma, dtype)
         scale_new = scale if np.any(np.isnan(chol)) else chol
         asc = np.linalg.norm(loc_new - loc) + np.linalg.norm(scale_new - scale, "fro")
     return ASSSState(itr, x_new, pe_new, ASSSAdaptState(loc_new, scale_new), asc, key), n_iter

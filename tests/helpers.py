@@ -61,3 +61,175 @@ def assert_state_bitequal(gpu_state, orc_state, what=""):
         bad = np.flatnonzero((av != bv).reshape(-1))
         assert bad.size == 0, (f"{what}: field {f} differs in {bad.size} of {av.size} entries; "
                                f"first at {bad[:5]}: gpu {a.reshape(-1)[bad[:5]]} oracle {b.reshape(-1)[bad[:5]]}")
+
+
+# ------------------------------------------------- NaN-aware bit comparison --
+ASSS_FIELDS = ("i", "z", "potential_energy", "loc", "scale", "as_change", "rng_key")
+
+
+def assert_bitequal_nan(a, b, what=""):
+    """Plain arrays: identical NaN positions, every other entry bit-identical
+    (sign of zero, +-inf and subnormals included).  NaN payload and sign are
+    not compared: x86 and gfx950 produce different default NaNs."""
+    a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    b = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    if b.dtype != a.dtype and a.dtype.kind in "iu" and b.dtype.kind in "iu":
+        b = b.astype(a.dtype)  # rng keys: int32 on the product side, uint32 on the oracle's
+    assert a.dtype.itemsize == b.dtype.itemsize and a.dtype.itemsize in (4, 8), (what, a.dtype, b.dtype)
+    bits = np.uint32 if a.dtype.itemsize == 4 else np.uint64
+    a, b = np.ascontiguousarray(a).reshape(-1), np.ascontiguousarray(b).reshape(-1)
+    ok = np.ones(a.size, bool)
+    if a.dtype.kind == "f" or b.dtype.kind == "f":
+        assert a.dtype == b.dtype, (what, a.dtype, b.dtype)
+        na, nb = np.isnan(a), np.isnan(b)
+        bad = np.flatnonzero(na != nb)
+        assert bad.size == 0, (f"{what}: NaN positions differ in {bad.size} of {a.size} entries; first at "
+                               f"{bad[:5]}: gpu {a[bad[:5]]} oracle {b[bad[:5]]}")
+        ok = ~na
+    bad = np.flatnonzero((a.view(bits) != b.view(bits)) & ok)
+    assert bad.size == 0, (f"{what}: differs in {bad.size} of {a.size} entries; first at {bad[:5]}: "
+                           f"gpu {a[bad[:5]]} oracle {b[bad[:5]]}")
+
+
+def _leaf(state, f):
+    """Field f of a product state (ARWMH or ASSS namedtuple) or of an orc.State."""
+    if hasattr(state, "adapt_state") and f in ("loc", "scale", "log_step_size"):
+        return getattr(state.adapt_state, f)
+    return getattr(state, f)
+
+
+def assert_state_bitequal_nan(gpu_state, orc_state, what="", fields=FIELDS):
+    """assert_state_bitequal for states that may hold NaN: per field the NaN
+    positions agree and every non-NaN entry is bit-identical.  `fields` takes
+    ASSS_FIELDS for an ASSS state (no step-size leaves)."""
+    for f in fields:
+        assert_bitequal_nan(_leaf(gpu_state, f), _leaf(orc_state, f), f"{what}: field {f}")
+
+
+# -------------------------------------------------------- edge scenarios ----
+EDGE_VALUES = (0.0, -0.0, 1e-45, -1e-45, 1e-38, 1e-20, 1.0, -1.0, 20.0, -20.0, 87.0, 88.8, 89.0, -87.0, -104.0,
+               200.0, -200.0, 1e4, -1e4, 1e19, -1e19, 3e38, -3e38, np.inf, -np.inf, np.nan)
+EDGE_ROW_VALUES = (1e-45, 1e19, 3e38, np.inf, np.nan)
+EDGE_REPS = 5  # seeded positions per value
+
+STEP_SIZE_CYCLE = (-110.0, -90.0, -20.0, 0.0, 20.0, 45.0, 88.0, 89.0)
+FACTOR_CYCLE = (1e-30, 1e-20, 1e-8, 1.0, 1e8, 1e15, 1e19, 1e25)
+# num_warmup of the hostile scenarios: hostile_adapt is applied at i = 5, so
+# steps 6-8 run with gamma_6..8 < 1 from the hostile values (loc decays from
+# 1e19 slowly), step 9 is the warmup reset (gamma_1 = 1: sqrt(1 - gamma) L = 0
+# -> keep L, loc jumps), and the schedule restarts after it
+HOSTILE_WARMUP = 8
+
+
+def log_scale_coords(kind, d):
+    """Coordinates a model exponentiates (log tau / log sigma)."""
+    return {"eight_schools": (1,), "kidiq": (3,), "diamonds": (d - 1,), "diamonds_ss": (d - 1,)}.get(kind, ())
+
+
+def edge_points(d, seed, hit=()):
+    """-> (torch [n, d], numpy [n, d]) float32, the same values: N(0, 1) rows
+    with one coordinate replaced in turn by each of EDGE_VALUES, at EDGE_REPS
+    seeded positions among the coordinates outside `hit` and once at every
+    coordinate of `hit` (log_scale_coords: each value reaches the exponentiated
+    coordinate exactly once per row set, so most rows keep a finite potential),
+    then rows with every coordinate at one of EDGE_ROW_VALUES."""
+    import torch
+    rng = np.random.default_rng(seed)
+    rows = []
+    with np.errstate(over="ignore", under="ignore"):
+        for v in EDGE_VALUES:
+            free = [r for r in range(d) if r not in hit] or list(range(d))
+            pos = [free[int(p)] for p in rng.integers(0, len(free), size=EDGE_REPS)] + [int(h) for h in hit]
+            for p in pos:
+                r = rng.normal(size=d).astype(np.float32)
+                r[p] = np.float32(v)
+                rows.append(r)
+        for v in EDGE_ROW_VALUES:
+            rows.append(np.full(d, v, np.float32))
+    z = np.stack(rows).astype(np.float32)
+    return torch.from_numpy(z.copy()), z
+
+
+def wild_starts(C, d, seed):
+    """-> (torch [C, d], numpy [C, d]) float32: N(0, 1) * 10^k with one seeded
+    integer k in [-3, 20] per chain."""
+    import torch
+    rng = np.random.default_rng(seed)
+    k = rng.integers(-3, 21, size=C)
+    z = (rng.normal(size=(C, d)) * (10.0 ** k)[:, None]).astype(np.float32)
+    return torch.from_numpy(z.copy()), z
+
+
+def hostile_adapt(state, step_size=True, factors=FACTOR_CYCLE, step_sizes=STEP_SIZE_CYCLE, loc_shift=1e19):
+    """Push the adaptation state of an orc.State (numpy, edited in place) or of
+    a product state (GPU tensors, edited in place from the same host
+    arithmetic, so both sides hold the same bits) to hostile values:
+    log_step_size cycles over STEP_SIZE_CYCLE by chain index, the packed factor
+    is multiplied per chain by factors[(chain // 8) % 8], loc += 1e19 on
+    the upper half of the chains.  step_size=False (ASSS) skips the step-size
+    leaf; factors / step_sizes / loc_shift replace the cycles and the shift
+    (the float64 step anchors of tests/test_edges.py shrink their top ends).
+    Returns the state."""
+    product = hasattr(state, "adapt_state")
+    loc, scale = _leaf(state, "loc"), _leaf(state, "scale")
+    C = loc.shape[0]
+    c = np.arange(C)
+    mult = np.asarray(factors, np.float32)[(c // 8) % 8]
+    lam = np.asarray(step_sizes, np.float32)[c % 8]
+
+    def edit(t, fn):
+        if product:
+            import torch
+            a = t.detach().cpu().numpy().copy()
+            fn(a)
+            t.copy_(torch.from_numpy(a))  # in place: bumps the version counter
+        else:
+            fn(t)
+
+    def mul_scale(a):
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            a *= mult[:, None]
+
+    def add_loc(a):
+        a[C // 2:] += np.float32(loc_shift)
+
+    edit(scale, mul_scale)
+    edit(loc, add_loc)
+    if step_size:
+        def set_lam(a):
+            a[:] = lam
+        edit(_leaf(state, "log_step_size"), set_lam)
+    return state
+
+
+# the model matrix of the edge tests (tests/test_edges.py, tests/test_gpu_edges.py)
+EDGE_MATRIX = [("gaussian", 1), ("gaussian", 5), ("gaussian", 33), ("gaussian", 64), ("gaussian", 72),
+               ("gaussian", 100), ("gaussian", 128), ("gaussian", 256), ("eight_schools", None), ("kidiq", None),
+               ("diamonds", None), ("diamonds_n77", None), ("diamonds_ss", None), ("mixture", 1), ("mixture", 3)]
+
+
+def make_edge_case(kind, d=None):
+    """make_case plus "diamonds_n77": the literal diamonds model off the
+    compile-time fast path (N = 77, K = 10; the generic split transition)."""
+    if kind == "diamonds_n77":
+        import orc
+        import posteriors as P
+        mk = P.synthetic_diamonds(N=77, K=10, seed=5)
+        arr, (N, K) = P.diamonds.pack_fn(mk)
+        return dict(model=P.diamonds), mk, orc.Model(orc.DIAMONDS, K + 1, arr, n_data=N, k_data=K)
+    return make_case(kind, d)
+
+
+def edge_init(kind, d, C, orc, seed=0, start="uniform"):
+    """Oracle-side start of an edge scenario -> (kw, mk, om, ost, z0): z0 is
+    uniform(-2, 2) (the benign start of tests/test_gpu_parity.py) or
+    wild_starts; every model takes it as flat init_params."""
+    kw, mk, om = make_edge_case(kind, d)
+    if start == "wild":
+        z0 = wild_starts(C, om.d, seed)[1]
+    else:
+        z0 = np.random.default_rng(seed).uniform(-2, 2, size=(C, om.d)).astype(np.float32)
+    from kernels_amd import PRNGKey
+    ost = orc.init(om, PRNGKey(seed), C, init_z=z0)
+    return kw, mk, om, ost, z0

@@ -189,3 +189,151 @@ def test_mmd2_on_reference_draws_full_size(gpu):
     want = ksum(x, x, True) / (n * (n - 1)) + ksum(y, y, True) / (m * (m - 1)) - 2 * ksum(x, y, False) / (n * m)
     got = E.mmd2_unbiased(x, y)
     assert got == pytest.approx(want, rel=1e-5)
+
+
+# ---- device math and the evaluation kernels at their edges -------------------
+U24 = 2.0 ** -24  # float32 unit roundoff
+
+
+@pytest.mark.parametrize("seed", [3, 1234567])
+def test_normals_bitexact(seed, gpu, orc):
+    """amh_normals (the library call behind _directions) bit for bit against
+    the host compile of include/amh_math.h: out[i] = N(Philox(i, 0, 0,
+    AMH_TAG_EVAL; key).v[0]).  This is the direct pin of the device compile of
+    Philox, amh_logf, sqrtf and both erfinv polynomials (the host compile is
+    pinned by tests/test_rng_math.py); at least 1000 of the 2^20 draws take the
+    tail polynomial (|u| > 0.9966)."""
+    import arwmh_np as lit
+    from kernels_amd import PRNGKey, _lib
+    from kernels_amd.random import as_key
+    n = 1 << 20
+    key = PRNGKey(seed)
+    z = torch.empty(n, dtype=torch.float32, device=gpu)
+    with torch.cuda.device(gpu.index):
+        _lib.check(_lib.lib().amh_normals(_lib.key_arr(as_key(key)), n, _lib.ptr(z), _lib.stream_ptr(gpu.index)))
+    torch.cuda.synchronize()
+    ctr = np.zeros((n, 4), np.uint32)
+    ctr[:, 0] = np.arange(n, dtype=np.uint32)
+    ctr[:, 3] = 0x4C415645  # AMH_TAG_EVAL
+    k = np.asarray(as_key(key)).astype(np.int64).astype(np.uint32).reshape(1, 2)
+    bits = orc.philox(ctr, np.repeat(k, n, axis=0))[:, 0].copy()
+    ref = orc.normal_from_bits(bits)
+    lo = np.float32(-0.99999994)
+    u = np.maximum(lit.unif01_from_bits(bits) * np.float32(2.0) + lo, lo)
+    assert int((np.abs(u) > 0.9966).sum()) >= 1000
+    assert np.isfinite(ref).all()
+    np.testing.assert_array_equal(z.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+def _edge_sets(n, m, d, kind, rng):
+    x = rng.normal(size=(n, d)).astype(np.float32)
+    y = (rng.normal(size=(m, d)) * 1.2 + 0.3).astype(np.float32)
+    if kind == "duplicates":  # exact zeros off the diagonal
+        y[: min(n, m)] = x[: min(n, m)][::-1]
+        x[n // 2:] = x[: n - n // 2]
+    return x, y
+
+
+EDGE_SHAPES = [(1, 1, 1), (1, 129, 32), (128, 128, 33), (127, 257, 64), (129, 1, 65), (130, 130, 31)]
+
+
+@pytest.mark.parametrize("kind", ["plain", "duplicates", "underflow"])
+@pytest.mark.parametrize("n,m,d", EDGE_SHAPES)
+def test_eval_kernels_edge_shapes(n, m, d, kind, gpu):
+    """_dist2, gaussian_kernel and _kernel_sum at the tile and staging
+    boundaries (kTile = 128, kKc = 32), n = 1 and m = 1, with duplicated points
+    and with a gamma that underflows exp for most pairs, against float64 numpy
+    on the same float32 inputs.  Tolerances are derived, per case:
+      * D2 is a sum of d non-negative fmaf terms (a - b)^2: relative
+        (d + 3) 2^-24, zeros exact;
+      * the exponent -gamma D2 then carries |gamma D2| (d + 4) 2^-24 = delta,
+        i.e. a relative expm1(delta) on exp, plus the exp's own error: 1.5 ulp
+        for amh_expf (tests/test_rng_math.py::test_expf; 2 ulp allowed for
+        torch.exp in gaussian_kernel), plus, below the normal range, an
+        absolute 1.2e-38 (a flushed subnormal);
+      * a kernel sum adds 64 x 2^-24 for the per-thread float32 partial sum of
+        64 values and is otherwise the per-pair bounds added up in float64.
+    At gamma = 1 / d the derived relative bounds are 0.9e-6 (d = 1) to 1.9e-5
+    (d = 64) on a kernel value and 4e-6 to 1.7e-5 on a sum: from d = 32 on
+    they exceed the 1e-5 of test_mmd2_unbiased_and_kernel, because the bound on
+    D2 is the worst case, linear in d, and exp turns the absolute error of
+    gamma D2 ~ 2.5 into a relative one (rounding errors observed grow like
+    sqrt(d) and stay below 1e-5).  With gamma = 60 / d (most pairs below the
+    normal range, exp -> 0) the relative bound reaches 1e-3 on the few values
+    that survive, |gamma D2| being ~150 there."""
+    from utils_amd import evaluation as E
+    rng = np.random.default_rng(1000 * n + 10 * m + d)
+    x, y = _edge_sets(n, m, d, kind, rng)
+    xd, yd = torch.as_tensor(x, device=gpu), torch.as_tensor(y, device=gpu)
+    x64, y64 = x.astype(np.float64), y.astype(np.float64)
+    gamma = float(np.float32(60.0 / d if kind == "underflow" else 1.0 / d))
+    cases = [(xd, yd, x64, y64, False)]
+    if n == m:
+        cases.append((xd, xd, x64, x64, True))  # the square case of mmd2_unbiased: diagonal skipped
+    for a, b, a64, b64, skip in cases:
+        ref = ((a64[:, None, :] - b64[None, :, :]) ** 2).sum(-1)
+        d2 = E._dist2(a, b).cpu().numpy().astype(np.float64)
+        assert d2.shape == ref.shape
+        assert np.all(np.abs(d2 - ref) <= (d + 3) * U24 * ref), np.max(np.abs(d2 - ref) / np.maximum(ref, 1e-300))
+        if kind == "duplicates":
+            # exact zeros off the diagonal too (a single point has no other pair)
+            assert (ref == 0).sum() > (len(ref) if skip and n > 1 else 0) and np.all(d2[ref == 0] == 0)
+        kref = np.exp(-gamma * ref)
+        delta = gamma * ref * (d + 4) * U24
+        K = E.gaussian_kernel(a, b, gamma).cpu().numpy().astype(np.float64)
+        tol_k = kref * (np.expm1(delta) + 4 * U24) + 1.2e-38
+        assert np.all(np.abs(K - kref) <= tol_k), np.max(np.abs(K - kref) / tol_k)
+        if kind == "underflow":
+            assert (kref < 1.2e-38).mean() > 0.5 or n * m == 1
+        mask = np.ones_like(kref)
+        if skip:
+            np.fill_diagonal(mask, 0.0)
+        want = float((kref * mask).sum())
+        tol_s = float(((kref * (np.expm1(delta) + 3 * U24 + 64 * U24) + 1.2e-38) * mask).sum())
+        got = E._kernel_sum(a, b, gamma, skip)
+        assert abs(got - want) <= tol_s, (got, want, tol_s)
+
+
+def _lse_ref(cost, pot, logw, eps):
+    from scipy.special import logsumexp
+    e = float(np.float32(eps))
+    lw = float(np.float32(logw))
+    arg = (pot.astype(np.float64)[None, :] - cost.astype(np.float64)) / e + lw
+    return -e * logsumexp(arg, axis=1), np.abs(arg - lw).max() + abs(lw)
+
+
+@pytest.mark.parametrize("eps", [1.0, 1e-3])
+@pytest.mark.parametrize("rows,cols", [(1, 1), (3, 63), (5, 64), (2, 257), (4, 1000)])
+def test_lse_half_edges(rows, cols, eps, gpu):
+    """_lse_half (lse_rows_kernel) against float64 scipy logsumexp: cols < 64
+    (lanes without a column), cols = 64, one past a block stride, four strides;
+    costs in [0, 50], so at eps = 1e-3 the arguments differ by far more than
+    the range of expf; and a row in which one column dominates by 1e4 / eps.
+
+    Tolerance eps (5 x 2^-24 A + 72 x 2^-24) on the output, A = max |(pot_j -
+    C_ij) / eps| + |log w|, derived from the running (max, sum) recurrence:
+    forming an argument takes three roundings of values <= A (3 u A, u =
+    2^-24), and log-sum-exp moves by at most the largest argument
+    perturbation.  Every combination step (<= 4 per thread at cols <= 1000, 6
+    shuffle levels, 3 wave merges: 13) rescales a partial sum by exp(-t), t the
+    distance to the new maximum, with t rounded (u t), the exp within 1 ulp
+    (2 u), one product and one sum (u each): relative to the total that is at
+    most e^-t (u t + 4 u) <= 4.4 u, 57 u over 13 steps; logf adds 1 ulp of
+    log S <= log 1000 (14 u), together 72 u.  M + log S and the product with
+    eps round once each (2 u A).  (The constant differs from the 8 x 2^-24 A +
+    1e-6 first guessed: fewer roundings scale with A, more do not.)"""
+    from utils_amd import evaluation as E
+    rng = np.random.default_rng(rows * 1000 + cols)
+    cost = rng.uniform(0, 50, size=(rows, cols)).astype(np.float32)
+    pot = rng.normal(size=cols).astype(np.float32)
+    logw = -float(np.log(cols))
+    variants = [(cost, pot)]
+    c2, p2 = cost.copy(), pot.copy()
+    p2[cols // 2] += np.float32(1e4)  # (pot_j - C_ij) / eps of one column ahead by 1e4 / eps
+    variants.append((c2, p2))
+    for cm, pt in variants:
+        got = E._lse_half(torch.as_tensor(cm, device=gpu), torch.as_tensor(pt, device=gpu), logw, eps)
+        ref, A = _lse_ref(cm, pt, logw, eps)
+        tol = float(np.float32(eps)) * (5 * U24 * A + 72 * U24)
+        err = np.abs(got.cpu().numpy().astype(np.float64) - ref)
+        assert np.all(np.isfinite(got.cpu().numpy())) and err.max() <= tol, (err.max(), tol)
