@@ -1121,9 +1121,11 @@ __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
 // ------------------------------------------------------------- launchers ----
 bool big_model(int model_id, int d) { return model_id == AMH_MODEL_GAUSSIAN && d > 64 && d <= 256; }
 // pooled mode: the MFMA path also takes d = 64 (every per-chain product is a
-// GEMM over chains once the factor is shared)
+// GEMM over chains once the factor is shared); the caller's potential
+// (amh_pooled_propose / amh_pooled_stats_external) follows the same forms,
+// so its sums go through the same update
 bool pooled_big_model(int model_id, int d) {
-  return model_id == AMH_MODEL_GAUSSIAN && d >= 64 && d <= 256 && d % 32 == 0;
+  return (model_id == AMH_MODEL_GAUSSIAN || model_id == AMH_MODEL_EXTERNAL) && d >= 64 && d <= 256 && d % 32 == 0;
 }
 
 // row slots per lane by d: two up to 128, three up to 192, four up to 256

@@ -814,6 +814,23 @@ static bool noise_ahead_off() {
 #endif
 }
 
+// the handle's chunk-partial scratch for n_chunks rows of vrow entries plus
+// the reduction's group sums (grown, never shrunk)
+static int grow_partials(amh_handle* h, int64_t n_chunks, int64_t vrow, void* stream, const char* where) {
+  const size_t need = (size_t)amh::pooled_scratch_rows(n_chunks) * (size_t)vrow * sizeof(double);
+  if (need <= h->partials_bytes) return AMH_OK;
+  if (h->partials) {
+    (void)hipStreamSynchronize((hipStream_t)stream);  // a queued launch may still use the old scratch
+    (void)hipFree(h->partials);
+  }
+  h->partials = nullptr;
+  h->partials_bytes = 0;
+  hipError_t e = hipMalloc(&h->partials, need);
+  if (e != hipSuccess) return hip_fail(h, e, where);
+  h->partials_bytes = need;
+  return AMH_OK;
+}
+
 // d = 64 with prep_for_update: the last step's chunk partials are left
 // unreduced; *deferred describes them for the update launch, which reduces
 // them first (one launch fewer per pooled block)
@@ -844,18 +861,7 @@ static int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled
   const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
   const int64_t n_chunks = big ? amh::pooled_big_chunks(num_chains, d) : (num_chains + chunk - 1) / chunk;
   const int64_t vrow = big ? amh::pooled_big_tile_V(d) : d + (int64_t)d * (d + 1) / 2 + 2;
-  const size_t need = (size_t)amh::pooled_scratch_rows(n_chunks) * (size_t)vrow * sizeof(double);
-  if (need > h->partials_bytes) {
-    if (h->partials) {
-      (void)hipStreamSynchronize((hipStream_t)stream);  // a queued launch may still use the old scratch
-      (void)hipFree(h->partials);
-    }
-    h->partials = nullptr;
-    h->partials_bytes = 0;
-    e = hipMalloc(&h->partials, need);
-    if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats/hipMalloc");
-    h->partials_bytes = need;
-  }
+  if (int rc = grow_partials(h, n_chunks, vrow, stream, "amh_pooled_stats/hipMalloc")) return rc;
   amh::PooledStatsParams p{};
   p.C = num_chains;
   p.d = d;
@@ -967,6 +973,70 @@ int amh_pooled_stats(amh_handle* h, int64_t num_chains, const amh_pooled_state* 
 int amh_pooled_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in, const amh_pooled_state* out,
                         int32_t k_steps, void* stream) {
   return pooled_update_impl(h, sums, in, out, k_steps, stream, false);
+}
+
+// The pooled transition around the caller's potential.  Nothing is kept in
+// the handle between the two calls: with the shared L the proposal is a
+// product over chains (no per-chain solves), and the accept pass reads the
+// proposals and regenerates u from (key, i + t).
+static int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
+                             const char* who, amh::PooledExtParams* p) {
+  if (!h) return fail(nullptr, AMH_EINVAL, std::string(who) + ": null handle");
+  if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, std::string(who) + ": needs AMH_MODEL_EXTERNAL");
+  const int d = h->cfg.dim;
+  if (d > 64 && !amh::pooled_big_model(h->model_id, d))
+    return fail(h, AMH_EINVAL, std::string(who) + ": d > 64 needs d % 32 == 0 in the pooled mode");
+  if (!pooled_ok(in) || num_chains < 1 || t < 0) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  *p = amh::PooledExtParams{};
+  p->C = num_chains;
+  p->d = d;
+  p->i = in->i;
+  p->t = t;
+  p->z = in->z;
+  p->pe = in->potential_energy;
+  p->keys = in->rng_key;
+  p->mu = in->loc;
+  p->L = in->scale;
+  p->lam = in->log_step_size;
+  p->eps = h->cfg.eps;
+  return AMH_OK;
+}
+
+int amh_pooled_propose(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, float* zprop,
+                       void* stream) {
+  amh::PooledExtParams p;
+  if (int rc = pooled_ext_params(h, num_chains, in, t, "amh_pooled_propose", &p)) return rc;
+  if (!zprop) return fail(h, AMH_EINVAL, "amh_pooled_propose: bad arguments");
+  hipError_t e = hipSetDevice(h->device);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_propose/hipSetDevice");
+  p.zprop = zprop;
+  e = amh::run_pooled_ext_propose(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_propose");
+  return AMH_OK;
+}
+
+int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
+                              const float* zprop, const float* pe_prop, float* z_out, float* pe_out, double* sums,
+                              int32_t accumulate, void* stream) {
+  amh::PooledExtParams p;
+  if (int rc = pooled_ext_params(h, num_chains, in, t, "amh_pooled_stats_external", &p)) return rc;
+  if (!zprop || !pe_prop || !z_out || !pe_out || !sums)
+    return fail(h, AMH_EINVAL, "amh_pooled_stats_external: bad arguments");
+  hipError_t e = hipSetDevice(h->device);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external/hipSetDevice");
+  const bool big = amh::pooled_big_model(h->model_id, p.d);
+  const int64_t vrow = big ? amh::pooled_big_tile_V(p.d) : p.d + (int64_t)p.d * (p.d + 1) / 2 + 2;
+  if (int rc = grow_partials(h, amh::pooled_ext_chunks(num_chains, p.d), vrow, stream,
+                             "amh_pooled_stats_external/hipMalloc"))
+    return rc;
+  p.zprop = const_cast<float*>(zprop);
+  p.pe_prop = pe_prop;
+  p.z_out = z_out;
+  p.pe_out = pe_out;
+  p.partials = h->partials;
+  e = amh::run_pooled_ext_stats(p, sums, accumulate != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external");
+  return AMH_OK;
 }
 
 }  // extern "C"

@@ -183,6 +183,33 @@ int64_t pooled_big_tile_V(int d);  // partial row length of the fused large-d st
 int64_t pooled_scratch_rows(int64_t n_chunks);  // partials + group sums of pooled_reduce
 hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float* pep, double* sums, hipStream_t s);
 hipError_t run_pooled_big_update(const PooledUpdateParams& p, hipStream_t s, bool sigma_ready = false);
+// chunk partials -> this rank's sums (accumulate: sums += them), d < 64:
+// double rows, group sums after the partials (pooled_scratch_rows); d >= 64:
+// float32 rows in the tile layout (pooled_big_tile_V)
+hipError_t pooled_reduce(const double* partials, int64_t n_chunks, int64_t V, double* sums, int accumulate,
+                         hipStream_t s, int tile_d = 0, FinalPrep fp = FinalPrep{});
+hipError_t launch_reduce_tiles(const float* partials, int64_t n_chunks, int64_t V, double* sums, int accumulate,
+                               int tile_d, const FinalPrep& fp, hipStream_t s);
+// The pooled transition split around the caller's potential
+// (AMH_MODEL_EXTERNAL; amh_pooled_ext.hip): step t of a block, proposals
+// written by the propose pass and read back, with U(zprop), by the stats pass
+struct PooledExtParams {
+  int64_t C;
+  int32_t d;
+  const int32_t* i;
+  int32_t t;
+  const float *z, *pe;
+  const uint32_t* keys;
+  const float *mu, *L, *lam;
+  float eps;
+  float* zprop;          // [C][d]
+  const float* pe_prop;  // [C] (stats)
+  float *z_out, *pe_out; // (stats; may alias z / pe)
+  double* partials;      // (stats) chunk partial rows + the reduction's scratch
+};
+int64_t pooled_ext_chunks(int64_t C, int d);
+hipError_t run_pooled_ext_propose(const PooledExtParams& p, hipStream_t s);
+hipError_t run_pooled_ext_stats(const PooledExtParams& p, double* sums, int accumulate, hipStream_t s);
 hipError_t run_asss_step(int model_id, const StepParams& p, hipStream_t s);  // amh_asss.hip
 hipError_t run_asss_step64(const StepParams& p, hipStream_t s);  // amh_kernels.hip (d = 64 Gaussian)
 hipError_t run_asss_pnx(int model_id, const AsssPnxParams& p, hipStream_t s);

@@ -15,60 +15,20 @@
 // The order of every sum is fixed (oracle: orc_pooled_stats/_update), so the
 // result does not depend on which CU runs which chunk.
 #include "amh_device.h"
+#include "amh_pooled_device.h"
 
 namespace amh {
 
 namespace {
 
-// Shared-factor row r as stored in LDS (dense, zero above the diagonal, rows
-// padded like the Gaussian precision) dotted with v broadcast from lane j:
-// partial sums over j mod 4, read 16 columns at a time.
-__device__ __forceinline__ float lds_row_dot64(uint32_t prow, int d, float v, bool act) {
-  using Gp = Grp<64>;
-  f32x2v y01 = {0.0f, 0.0f}, y23 = {0.0f, 0.0f};
-  static_for<4>([&](auto B) {
-    constexpr int b = B;
-    if (16 * b < d) {
-      f32x4 pv[4];
-      static_for<4>([&](auto Q) {
-        pv[Q] = (4 * (4 * b + Q) < d) ? lds_ld4<16 * (4 * b + Q)>(prow) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      });
-      lds_wait(pv[0], pv[1], pv[2], pv[3]);
-      // columns (j, j+1) through one v_pk_fma_f32 into accumulators (j mod 4,
-      // j+1 mod 4); a column past d adds 0 * 0 (padded row, inactive lane)
-      static_for<8>([&](auto K2) {
-        constexpr int j = 16 * b + 2 * K2;
-        if (j < d) {
-          const f32x4 q = pv[K2 / 2];
-          const f32x2v pp = (K2 % 2 == 0) ? f32x2v{q[0], q[1]} : f32x2v{q[2], q[3]};
-          const f32x2v pa = act ? pp : f32x2v{0.0f, 0.0f};
-          const f32x2v bp = {Gp::template bcast<j>(v), Gp::template bcast<j + 1>(v)};
-          if constexpr (K2 % 2 == 0) {
-            y01 = __builtin_elementwise_fma(pa, bp, y01);
-          } else {
-            y23 = __builtin_elementwise_fma(pa, bp, y23);
-          }
-        }
-      });
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-  return (y01[0] + y01[1]) + (y23[0] + y23[1]);
-}
-
-__host__ __device__ inline int pooled_ld(int d) { return ((d + 3) & ~3) + 4; }
-
 template <template <int> class M>
 __host__ __device__ inline size_t pooled_lds_model_floats(const ModelArgs& m, int d) {
   return (M<64>::lds_bytes(m, d) / sizeof(float) + 3) & ~(size_t)3;
 }
-// combine-tree slot: rows r = 0..63 as [S_r0 .. S_rr, sd_r], then sa
-constexpr int kTreeSlot = 64 * 65 / 2 + 64 + 1;
-
 template <template <int> class M>
 __host__ __device__ inline size_t pooled_lds_bytes(const ModelArgs& m, int d) {
   const size_t f = pooled_lds_model_floats<M>(m, d) + (size_t)d * pooled_ld(d);
-  return (f + (size_t)(kPoolWaves / 2) * kTreeSlot) * sizeof(float);
+  return (f + kPooledTreeFloats) * sizeof(float);
 }
 
 }  // namespace
@@ -76,7 +36,6 @@ __host__ __device__ inline size_t pooled_lds_bytes(const ModelArgs& m, int d) {
 template <template <int> class M, bool EXACT>
 __global__ __launch_bounds__(kPoolWaves * 64) void pooled_stats_kernel(PooledStatsParams p) {
   constexpr int G = 64;
-  using Gp = Grp<G>;
   extern __shared__ float lds[];
   const int d = EXACT ? 64 : p.d;
   const int ld = pooled_ld(d);
@@ -86,14 +45,10 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_stats_kernel(PooledSta
   float* tree = lrow + (size_t)d * ld;
 
   M<G>::stage(lds, p.model, d);
-  for (int k = threadIdx.x; k < d * ld; k += blockDim.x) {
-    const int row = k / ld, col = k - row * ld;
-    lrow[k] = (col <= row && col < d) ? p.L[col_off(d, col) + (row - col)] : 0.0f;
-  }
+  pooled_stage_factor(lrow, p.L, d);
   __syncthreads();
 
-  const int lane = lane_id();
-  const int r = lane;
+  const int r = lane_id();
   const bool act = r < d;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
   const auto mctx = M<G>::prepare(p.model, d, r);
@@ -148,72 +103,18 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_stats_kernel(PooledSta
       // pooled statistics (float32 over this wave's chain-steps: chains in
       // order, each chain's K steps in order)
       const float delta = act ? z - mu : 0.0f;
-      sd = sd + delta;
-      // (S_k, S_k+1) += delta_r (delta_k, delta_k+1): one v_pk_fma_f32 per pair
-      // (each half is the same fmaf; past d the broadcast delta is 0)
-      static_for<32>([&](auto K2) {
-        constexpr int k = 2 * K2;
-        if (k < d) {
-          const f32x2v bp = {Gp::template bcast<k>(delta), Gp::template bcast<k + 1>(delta)};
-          const f32x2v sp = __builtin_elementwise_fma(f32x2v{delta, delta}, bp, f32x2v{S[k], S[k + 1]});
-          S[k] = sp[0];
-          S[k + 1] = sp[1];
-        }
-        column_fence<k + 1>();
-      });
+      pooled_accumulate(S, sd, delta, d);
       sa = sa + alpha;
     }
     const Buf bo(uniform_ptr(p.z_out + c * d), 4u * (uint32_t)d);
     bo.st(z, vr, 0);
     if (r == 0) p.pe_out[c] = pe;
   }
-  // The chunk's 16 wave partials are combined by a fixed pairwise tree in
-  // float32 (h = 8, 4, 2, 1: wave w < h adds wave w + h), through LDS slots
-  // holding each row r as [S_r0 .. S_rr, sd_r] (row offset r(r+3)/2) and sa
-  // last; the chunk total is then written in double (oracle mirror).
-  const uint32_t rowoff = (uint32_t)(r * (r + 3) / 2);
-  static_for<4>([&](auto H) {
-    constexpr int h = 8 >> H;
-    if (w >= h && w < 2 * h) {
-      float* slot = tree + (size_t)(w - h) * kTreeSlot;
-      if (act) {
-        static_for<64>([&](auto K) {
-          constexpr int k = K;
-          if (k <= r) slot[rowoff + k] = S[k];
-        });
-        slot[rowoff + r + 1] = sd;
-      }
-      if (lane == 0) slot[kTreeSlot - 1] = sa;
-    }
-    __syncthreads();
-    if (w < h) {
-      const float* slot = tree + (size_t)w * kTreeSlot;
-      if (act) {
-        static_for<64>([&](auto K) {
-          constexpr int k = K;
-          if (k <= r) S[k] = S[k] + slot[rowoff + k];
-        });
-        sd = sd + slot[rowoff + r + 1];
-      }
-      sa = sa + slot[kTreeSlot - 1];
-    }
-    __syncthreads();
-  });
-  if (w == 0) {
-    double* out = p.partials + (int64_t)blockIdx.x * V;
-    if (act) {
-      static_for<64>([&](auto K) {
-        constexpr int k = K;
-        if (k <= r) out[d + col_off(d, k) + (r - k)] = (double)S[k];
-      });
-      out[r] = (double)sd;
-    }
-    if (lane == 0) {
-      const int64_t left = p.C - chunk0;
-      out[d + P] = (double)sa;
-      out[d + P + 1] = (double)K * (double)(left < (int64_t)kPoolWaves * cpw ? left : (int64_t)kPoolWaves * cpw);
-    }
-  }
+  // the 16 wave partials -> the chunk's partial row (fixed float32 tree, then double)
+  const int64_t left = p.C - chunk0;
+  const int64_t full = (int64_t)kPoolWaves * cpw;
+  pooled_chunk_out(S, sd, sa, tree, r, act, w, d, p.partials + (int64_t)blockIdx.x * V,
+                   (double)K * (double)(left < full ? left : full));
 }
 
 // Chunk partials -> sums, in a fixed two-level order (oracle mirror):
@@ -275,7 +176,7 @@ int64_t pooled_scratch_rows(int64_t n_chunks) { return n_chunks + (n_chunks + kR
 // d >= 64 reduces its float32 tile rows in one launch
 // (amh_big_pooled.hip, pooled_reduce_tiles_kernel)
 hipError_t pooled_reduce(const double* partials, int64_t n_chunks, int64_t V, double* sums, int accumulate,
-                         hipStream_t s, int tile_d = 0, FinalPrep fp = FinalPrep{}) {
+                         hipStream_t s, int tile_d, FinalPrep fp) {
   const int64_t n_groups = (n_chunks + kRedGroup - 1) / kRedGroup;
   double* gsum = const_cast<double*>(partials) + n_chunks * V;
   const unsigned vb = (unsigned)((V + 255) / 256);

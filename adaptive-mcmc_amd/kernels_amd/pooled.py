@@ -47,6 +47,18 @@ class PooledARWMH(ARWMH):
     torch.distributed process group whose chains are pooled (default: the
     default group when initialised, else this process alone).
 
+    potential_fn may be a registry potential (fused into the pooled kernels)
+    or any batched torch callable z [n, d] -> U [n], at the pooled mode's
+    dimensions (d <= 64 or a multiple of 32 up to 256).  A callable runs
+    between two launches per transition: amh_pooled_propose writes every
+    chain's proposal with the shared state, the callable evaluates U there,
+    and amh_pooled_stats_external accepts and forms the step's sums, bit for
+    bit what the fused kernels give for the same U.  A block of sync_every =
+    K steps is K such rounds, the block's sums s_0 + s_1 + ... in step order
+    (up to d = 64 the fused kernels associate a block's sums
+    differently).  Everything after the sums (all-reduce, update, overlap) is
+    shared with the registry path.
+
     sync_every = K pools every K transitions: the shared
     state is frozen for a block of K transitions of every chain, the sums
     (and, across ranks, the one all-reduce) cover the block's K * C
@@ -207,8 +219,30 @@ class PooledARWMH(ARWMH):
             c, self._rccl_comm = self._rccl_comm, None
             c.close()
 
+    def _stats_external(self, L, cin, sout, buf, C):
+        """AMH_MODEL_EXTERNAL: the block's K transitions as K rounds of
+        amh_pooled_propose, the caller's U of the proposals, and
+        amh_pooled_stats_external (accept + the round's sums, added to the
+        block's in step order).  Rounds after the first read the z / pe the
+        previous one wrote, with the frozen shared state of `cin`."""
+        dev = sout.z.device
+        h, st = self._handle.h, _lib.stream_ptr(dev.index)
+        zp = torch.empty(C, self._dim, dtype=torch.float32, device=dev)
+        cur = cin
+        for t in range(self.sync_every):
+            _lib.check(L.amh_pooled_propose(h, C, ctypes.byref(cur), t, _lib.ptr(zp), st), h)
+            pe = self._potential_fn.evaluate(zp)
+            _lib.check(L.amh_pooled_stats_external(h, C, ctypes.byref(cur), t, _lib.ptr(zp), _lib.ptr(pe),
+                                                   _lib.ptr(sout.z), _lib.ptr(sout.potential_energy), _lib.ptr(buf),
+                                                   int(t > 0), st), h)
+            if t == 0 and self.sync_every > 1:
+                cur = AmhPooledState.from_buffer_copy(cin)
+                cur.z, cur.potential_energy = sout.z.data_ptr(), sout.potential_energy.data_ptr()
+
     def _stats(self, L, cin, sout, buf, C):
         dev = sout.z.device.index
+        if self._external():
+            return self._stats_external(L, cin, sout, buf, C)
         _lib.check(L.amh_pooled_stats_k(self._handle.h, C, ctypes.byref(cin), self.sync_every, _lib.ptr(sout.z),
                                         _lib.ptr(sout.potential_energy), _lib.ptr(buf), _lib.stream_ptr(dev)),
                    self._handle.h)
@@ -315,7 +349,7 @@ class PooledARWMH(ARWMH):
         K = self.sync_every
         if int(n_steps) % K != 0:
             raise ValueError(f"n_steps ({n_steps}) must be a multiple of sync_every ({K})")
-        if self._world() == 1 and not self.overlap and not self.force_collective:
+        if self._world() == 1 and not self.overlap and not self.force_collective and not self._external():
             L = _lib.lib()
             dev = state.z.device.index
             c = self._c(state)

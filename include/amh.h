@@ -304,6 +304,41 @@ int amh_pooled_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_state*
                       const amh_pooled_state* out, int32_t n_steps, int32_t sync_every, double* sums,
                       void* stream);
 
+/* The pooled transition with the caller's potential (AMH_MODEL_EXTERNAL; any
+ * other model returns AMH_EINVAL): amh_pooled_stats split around U, the pooled
+ * counterpart of amh_propose / amh_step_external.  d <= 64, or a multiple of
+ * 32 up to 256.  Step t of a block (t = 0 when sync_every = 1):
+ *   amh_pooled_propose         zprop[C][d] = z + fmaf(e^lam, L xi, eps xi) with
+ *                              the shared (L, lam) of `in`, the noise of every
+ *                              chain at stream position in->i[0] + t
+ *                              (arwmh.py:162-167)
+ *   the caller                 pe_prop[C] = U(zprop)
+ *   amh_pooled_stats_external  accept (NaN -> +inf, arwmh.py:171-178; u from
+ *                              the same stream position), z / pe to z_out /
+ *                              pe_out (may alias in->z / in->potential_energy)
+ *                              and this rank's sums of the step, S_d, S_dd,
+ *                              S_a, N; accumulate != 0: sums += them.
+ * Per chain and per sum the result is amh_pooled_stats' with pe_prop in place
+ * of the in-kernel potential (d < 64 the lane-per-row form, d >= 64 the MFMA
+ * form with 128-chain chunks), and amh_pooled_update_k consumes the sums
+ * unchanged.  A block of K = sync_every steps is K rounds propose -> U ->
+ * accept, `in` the frozen shared state with z / pe of the previous round,
+ * accumulate = (t > 0): each round reduces its own s_t completely and
+ * sums = s_0, then sums + s_t in step order.  That is amh_pooled_stats_k's
+ * order above d = 64; up to d = 64 the fused kernels associate a block's sums
+ * differently (chain-steps inside the chunk), so there an external block
+ * equals K single-step calls added in step order, not amh_pooled_stats_k.
+ * Nothing is kept in the handle between the calls: the shared L makes the
+ * proposal a product over chains with no per-chain solves to remember, so
+ * (unlike amh_step_external above d = 64) there is no "proposals of this
+ * state" contract -- any zprop / pe_prop pair formed from `in` at step t is
+ * taken. */
+int amh_pooled_propose(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
+                       float* zprop, void* stream);
+int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
+                              const float* zprop, const float* pe_prop, float* z_out, float* pe_out,
+                              double* sums, int32_t accumulate, void* stream);
+
 /* The exchange between amh_pooled_stats_k and amh_pooled_update_k on N > 1
  * ranks (SURVEY.md §8(b) amh_pooled_allreduce; no counterpart in the
  * reference, whose adaptation is per chain): in-place ncclAllReduce(sum) of
