@@ -1980,14 +1980,11 @@ int64_t pooled_big_chunks(int64_t C, int d) {
   return (C + ch - 1) / ch;
 }
 
-hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float* pep, double* sums, hipStream_t s) {
+hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* pack, double* sums, hipStream_t s) {
   const int d = p.d;
-  const int64_t V = d + (int64_t)d * (d + 1) / 2 + 2;
   if (d == kF) {  // one launch (+ the reduction) per step
     const int64_t nch = pooled_big_chunks(p.C, d);
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     const int64_t grid = nch < 2 * (int64_t)cus ? nch : 2 * (int64_t)cus;  // persistent, two per CU
     if (p.k_steps > 1)
       hipLaunchKernelGGL(pooled_fused64_kernel<true>, dim3((unsigned)grid), dim3(256), fused64_lds_bytes(), s, p, nch);
@@ -1995,7 +1992,6 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float*
       hipLaunchKernelGGL(pooled_fused64_kernel<false>, dim3((unsigned)grid), dim3(256), fused64_lds_bytes(), s, p, nch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    (void)V;
     if (p.defer_reduce) return hipSuccess;  // the update launch reduces (run_pooled_big_update)
     return launch_reduce_tiles((const float*)p.partials, nch, pooled_big_tile_V(d), sums, p.accumulate, d, FinalPrep{},
                                s);
@@ -2003,7 +1999,6 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float*
   {
     const int nt = d / 32;
     const int64_t nch = pooled_big_chunks(p.C, d);
-    float* pack = xprop;  // the caller's scratch: pooled_big_pack_floats(d) floats
     hipError_t e = hipSuccess;
     if (!p.pack_ready) {
       hipLaunchKernelGGL(pooled_pack_kernel, dim3((unsigned)(nt * (nt + 1) / 2 + nt * nt)), dim3(256), 0, s, p.L,
@@ -2011,9 +2006,7 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float*
       e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     const int64_t grid = nch < (int64_t)cus ? nch : (int64_t)cus;
     switch (nt) {
 #define AMH_FB(NT_)                                                                                          \
@@ -2028,14 +2021,13 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float*
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    (void)pep;
     // one launch (was pooled_group4_kernel + pooled_final_kernel)
     return launch_reduce_tiles((const float*)p.partials, nch, pooled_big_tile_V(d), sums, p.accumulate, d, p.prep, s);
   }
 }
 
 hipError_t run_pooled_big_update(const PooledUpdateParams& p, hipStream_t s, bool sigma_ready) {
-  const size_t shm = (size_t)p.d * (p.d + 4) / 2 * sizeof(float);
+  const size_t shm = pooled_factor_floats(p.d) * sizeof(float);
   hipError_t e = hipSuccess;
   const bool in_block = p.d == 64;  // d = 64: prep and post run inside the update block
   if (!sigma_ready && !in_block) {  // else pooled_final_kernel formed Sigma' already
@@ -2050,9 +2042,7 @@ hipError_t run_pooled_big_update(const PooledUpdateParams& p, hipStream_t s, boo
     const unsigned head = p.red_blocks > 0 ? (unsigned)p.red_blocks : 1u;
     unsigned nb = head;
     if (p.noise_C > 0 && p.xi != nullptr) {
-      int dev = 0, cus = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+      const int cus = cu_count();
       nb = (unsigned)cus > head + 1 ? (unsigned)cus : head + 1;
     }
     hipLaunchKernelGGL(pooled_update64_kernel, dim3(nb), dim3(512), 0, s, p);
@@ -2060,9 +2050,7 @@ hipError_t run_pooled_big_update(const PooledUpdateParams& p, hipStream_t s, boo
   }
   unsigned nblk = 1;  // + one noise block per other CU when the next step's noise is drawn ahead
   if (p.noise_C > 0 && p.xi != nullptr) {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     nblk = (unsigned)(cus > 1 ? cus : 2);
   }
   switch (p.d / 32) {

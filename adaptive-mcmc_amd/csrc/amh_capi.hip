@@ -1,20 +1,43 @@
 // amh_capi.hip -- the extern "C" boundary of libamh.so (include/amh.h).
 // Validates arguments, keeps per-handle configuration and model binding, and
 // enqueues the kernels of amh_kernels.hip on the caller's stream.
+// Layout: the handle and its helpers, then one extern "C" region per family
+// (core, external potential, ASSS, evaluation, pooled covariance, diagnostics),
+// each preceded by the helpers only that family uses.
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/amh.h"
 #include "../../include/amh_math.h"
 #include "amh_internal.h"
 
-#include <vector>
+namespace amh {
+
+// device scratch owned by a handle: grown on demand, never shrunk
+struct Scratch {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+
+  template <class T>
+  T* as() const { return static_cast<T*>(ptr); }
+  // at least `need` bytes, reported as `who`; zero_fresh: a new allocation starts zeroed
+  int grow(amh_handle* h, size_t need, void* stream, const char* who, bool zero_fresh = false);
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+  }
+};
+
+}  // namespace amh
 
 struct amh_handle {
   amh_config cfg;
@@ -23,19 +46,16 @@ struct amh_handle {
   amh::ModelArgs model{nullptr, 0, 0};
   int64_t n_data = 0;
   float* gamma_tab = nullptr;  // device, kGammaTab entries
-  double* partials = nullptr;  // pooled mode: chunk partial sums (scratch)
-  size_t partials_bytes = 0;
-  float* split_buf = nullptr;  // split path: proposals [C][d] then U(z') [C] (scratch)
-  int64_t big_ready_C = -1;    // d > 64: split_buf holds the next proposal of the last output state (C chains)
-  amh_state big_ready_out{};   // ... and that output state's buffers: READY is honoured only for these
-  int64_t ext_ready_C = -1;    // external potential, d > 64: split_buf holds the solves (wa, wr, dg) of
-  amh_state ext_ready_in{};    // the proposals formed from this state (amh_propose / amh_step_external)
-  size_t split_bytes = 0;
-  float* upd_buf = nullptr;    // pooled d > 64: Sigma' / L' staging (4-row-aligned layout) + ok flag
-  size_t upd_bytes = 0;
   float* xpack = nullptr;      // diamonds: design matrix in MFMA tile order (made by amh_bind_model)
-  float* noise_buf = nullptr;  // pooled d > 64: [cap] records (i, key0, key1, u bits) then xi [cap][d]
-  size_t noise_bytes = 0;
+  amh::Scratch partials;       // pooled mode: chunk partial sums
+  amh::Scratch split;          // split path: proposals [C][d] then U(z') [C]; d > 64: xprop, wa, wr, dg [C][d]
+                               // then U(z') [C]; pooled d > 64: the A-operand copies (pooled_big_pack_floats)
+  int64_t big_ready_C = -1;    // d > 64: split holds the next proposal of the last output state (C chains)
+  amh_state big_ready_out{};   // ... and that output state's buffers: READY is honoured only for these
+  int64_t ext_ready_C = -1;    // external potential, d > 64: split holds the solves (wa, wr, dg) of
+  amh_state ext_ready_in{};    // the proposals formed from this state (amh_propose / amh_step_external)
+  amh::Scratch upd;            // pooled d >= 64: Sigma' / L' staging (pooled_update_scratch_floats)
+  amh::Scratch noise;          // pooled d >= 64: [cap] records (i, key0, key1, u bits) then xi [cap][d]
   int64_t noise_cap = 0;       // chains the noise buffer holds
   int64_t noise_C = 0;         // chains of the last stats call, whose keys are at noise_keys
   const uint32_t* noise_keys = nullptr;
@@ -53,9 +73,28 @@ int fail(amh_handle* h, int code, const std::string& msg) {
   return code;
 }
 
-int hip_fail(amh_handle* h, hipError_t e, const char* where) {
-  return fail(h, AMH_EHIP, std::string(where) + ": " + hipGetErrorString(e));
+int hip_fail(amh_handle* h, hipError_t e, const std::string& where) {
+  return fail(h, AMH_EHIP, where + ": " + hipGetErrorString(e));
 }
+
+}  // namespace
+
+// a queued launch may still read the old buffer, so the stream drains before the free
+int amh::Scratch::grow(amh_handle* h, size_t need, void* stream, const char* who, bool zero_fresh) {
+  if (need <= bytes) return AMH_OK;
+  if (ptr) (void)hipStreamSynchronize((hipStream_t)stream);
+  release();
+  hipError_t e = hipMalloc(&ptr, need);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipMalloc");
+  bytes = need;
+  if (zero_fresh) {
+    e = hipMemsetAsync(ptr, 0, bytes, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipMemsetAsync");
+  }
+  return AMH_OK;
+}
+
+namespace {
 
 const char* const kUpdateStuck =
     "amh_pooled_update (d = 64): a factoring wave's bounded wait for an earlier wave's columns ran out in an "
@@ -68,6 +107,21 @@ int check_device_flag(amh_handle* h) {
     *(volatile int*)h->err_host = 0;
     return fail(h, AMH_EHIP, kUpdateStuck);
   }
+  return AMH_OK;
+}
+
+// every entry's first checks, reported under the entry's public name `who`
+int enter(amh_handle* h, const char* who, bool needs_model) {
+  if (!h) return fail(nullptr, AMH_EINVAL, std::string(who) + ": null handle");
+  if (needs_model && !h->model_id) return fail(h, AMH_ENOMODEL, std::string(who) + ": no model bound");
+  return AMH_OK;
+}
+
+// ... and its last one before it enqueues work: after the argument checks, so
+// that a refused call leaves the thread's current device alone
+int use_device(amh_handle* h, const char* who) {
+  const hipError_t e = hipSetDevice(h->device);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipSetDevice");
   return AMH_OK;
 }
 
@@ -128,24 +182,105 @@ int expected_dim(int model_id, int64_t n_data, const int64_t* ip, int nip, int d
   }
 }
 
-// device scratch of at least `need` bytes (grown, never shrunk); a queued
-// launch may still read the old buffer, so the stream drains before the free
-int grow(amh_handle* h, float** buf, size_t* have, size_t need, void* stream, const char* where) {
-  if (need <= *have) return AMH_OK;
-  if (*buf) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(*buf);
+// ---- kernel parameters from the handle ----
+// the fields StepParams and BigParams share: the configuration, the state
+// buffers of one call over C chains and its optional collection
+template <class P>
+P handle_params(const amh_handle* h, int64_t C, const amh_state& in, const amh_state& out,
+                const amh_collect* collect) {
+  P p{};
+  p.in = in;
+  p.out = out;
+  p.C = C;
+  p.d = h->cfg.dim;
+  p.W = h->cfg.num_warmup;
+  p.a = h->cfg.lr_decay;
+  p.target = h->cfg.target_accept_prob;
+  p.eps = h->cfg.eps;
+  p.gamma_tab = h->gamma_tab;
+  p.gamma_tab_n = amh::kGammaTab;
+  p.col_z = collect ? collect->z : nullptr;
+  p.col_pe = collect ? collect->potential_energy : nullptr;
+  p.accept_count = collect ? collect->accept_count : nullptr;
+  return p;
+}
+
+amh::StepParams step_params(const amh_handle* h, int64_t C, const amh_state& in, const amh_state& out,
+                            int32_t n_steps, const amh_collect* collect) {
+  amh::StepParams p = handle_params<amh::StepParams>(h, C, in, out, collect);
+  p.n_steps = n_steps;
+  p.thinning = collect ? collect->thinning : 1;
+  p.model = h->model;
+  return p;
+}
+
+// the scratch pointers (xprop, wa, wr, dg, pep) are the caller's to set
+amh::BigParams big_params(const amh_handle* h, int64_t C, const amh_state& in, const amh_state& out,
+                          const amh_collect* collect) {
+  return handle_params<amh::BigParams>(h, C, in, out, collect);
+}
+
+// ---- one transition per launch sequence ----
+// collection of a call `p` that is issued one transition at a time: step t
+// keeps slot t / thinning iff (t + 1) % thinning == 0, and writes none otherwise
+struct Slot {
+  float *z, *pe;
+};
+
+Slot collect_slot(const amh::StepParams& p, int32_t t) {
+  if ((t + 1) % p.thinning != 0) return {nullptr, nullptr};
+  const size_t k = (size_t)(t / p.thinning);
+  return {p.col_z ? p.col_z + k * (size_t)p.C * p.d : nullptr, p.col_pe ? p.col_pe + k * (size_t)p.C : nullptr};
+}
+
+// The call `p` as n_steps chained transitions over the handle's split scratch
+// of floats_per_chain floats per chain (d > 64, and the literal diamonds split
+// path).  transition(in, slot, propose, next) enqueues one transition from
+// state `in`: the propose pass if `propose`, the potential of the proposals,
+// and the step pass, which also forms the next transition's proposal if `next`
+// (so the factor is read once per transition).  Only the first transition of
+// a call may need the propose pass: not when the caller vouches
+// (AMH_STEP_PROPOSAL_READY) that `in` is the unchanged output of the previous
+// call, which kept its next proposal in the scratch (AMH_STEP_KEEP_PROPOSAL),
+// and `in` is the very buffers that call wrote.
+template <class Transition>
+int run_chained(amh_handle* h, const amh::StepParams& p, size_t floats_per_chain, int32_t flags, void* stream,
+                const char* where, Transition transition) {
+  const size_t need = (size_t)p.C * floats_per_chain * sizeof(float);
+  // a proposal kept for C chains means the scratch held `need` bytes already; it
+  // can have grown since only if an allocation failed, and then holds nothing
+  const bool grown = need > h->split.bytes;
+  if (int rc = h->split.grow(h, need, stream, "amh_step")) return rc;
+  const bool ready = !grown && (flags & AMH_STEP_PROPOSAL_READY) && h->big_ready_C == p.C &&
+                     same_buffers(p.in, h->big_ready_out);
+  const bool keep_next = (flags & AMH_STEP_KEEP_PROPOSAL) != 0;
+  h->big_ready_C = -1;
+  for (int32_t t = 0; t < p.n_steps; ++t) {
+    const hipError_t e =
+        transition(t == 0 ? p.in : p.out, collect_slot(p, t), t == 0 && !ready, t + 1 < p.n_steps || keep_next);
+    if (e != hipSuccess) return hip_fail(h, e, where);
   }
-  *buf = nullptr;
-  *have = 0;
-  hipError_t e = hipMalloc(buf, need);
-  if (e != hipSuccess) return hip_fail(h, e, where);
-  *have = need;
+  h->big_ready_C = keep_next ? p.C : -1;
+  h->big_ready_out = p.out;
   return AMH_OK;
+}
+
+// A/B switches of the diagnostic build only (-DAMH_DIAG, `make stamps`; the
+// bits are the same either way, the release library reads no environment):
+// NAME=0 turns the optimisation off
+bool diag_env_off(const char* name) {
+#ifdef AMH_DIAG
+  const char* e = getenv(name);
+  return e != nullptr && e[0] == '0';
+#else
+  (void)name;
+  return false;
+#endif
 }
 
 }  // namespace
 
+// -------------------------------------------------------------------- core --
 extern "C" {
 
 int amh_version(void) { return AMH_ABI_VERSION; }
@@ -182,7 +317,7 @@ int amh_create(const amh_config* cfg, int device, amh_handle** out) {
 }
 
 int amh_check_device(amh_handle* h) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_check_device: null handle");
+  if (int rc = enter(h, "amh_check_device", false)) return rc;
   return check_device_flag(h);
 }
 
@@ -196,11 +331,8 @@ int amh_destroy(amh_handle* h) {
     // hipFree below orders the frees after outstanding work as HIP defines.
     if (h->err_host && *(volatile int*)h->err_host != 0) rc = fail(nullptr, AMH_EHIP, kUpdateStuck);
     if (h->gamma_tab) (void)hipFree(h->gamma_tab);
-    if (h->partials) (void)hipFree(h->partials);
-    if (h->split_buf) (void)hipFree(h->split_buf);
-    if (h->upd_buf) (void)hipFree(h->upd_buf);
     if (h->xpack) (void)hipFree(h->xpack);
-    if (h->noise_buf) (void)hipFree(h->noise_buf);
+    for (amh::Scratch* s : {&h->partials, &h->split, &h->upd, &h->noise}) s->release();
     if (h->err_host) (void)hipHostFree(h->err_host);
   }
   delete h;
@@ -209,7 +341,7 @@ int amh_destroy(amh_handle* h) {
 
 int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n_data, const int64_t* iparams,
                    int32_t n_iparams) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_bind_model: null handle");
+  if (int rc = enter(h, "amh_bind_model", false)) return rc;
   if (!data) return fail(h, AMH_EINVAL, "amh_bind_model: null data");
   std::string why;
   const int dm = expected_dim(model_id, n_data, iparams, n_iparams, h->cfg.dim, &why);
@@ -221,8 +353,7 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
     return fail(h, AMH_EINVAL, "amh_bind_model: d > 64 needs the Gaussian model or an external potential (d <= 256)");
   // the handle's device for everything below (the caller -- Handle.bind_model --
   // holds it current and restores its own afterwards)
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_bind_model/hipSetDevice");
+  if (int rc = use_device(h, "amh_bind_model")) return rc;
   if (h->xpack) {
     (void)hipDeviceSynchronize();  // a queued launch may still read the old copy
     (void)hipFree(h->xpack);
@@ -239,7 +370,7 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
     // on the null stream: the caller has synchronised the stream that wrote data)
     const int64_t nf = amh::diamonds_pack_floats(h->model.n, h->model.k);
     if (nf > 0) {
-      e = hipMalloc(&h->xpack, (size_t)nf * sizeof(float));
+      hipError_t e = hipMalloc(&h->xpack, (size_t)nf * sizeof(float));
       if (e == hipSuccess) e = amh::run_diamonds_pack(h->model, h->xpack, nullptr);
       if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
       if (e != hipSuccess) {
@@ -255,14 +386,12 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
 
 int amh_init(amh_handle* h, const uint32_t key[2], int64_t chain_offset, int64_t num_chains, const float* init_z,
              const amh_state* out, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_init: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_init: no model bound");
+  if (int rc = enter(h, "amh_init", true)) return rc;
   if (!key || !state_ok(out) || num_chains < 1 || chain_offset < 0)
     return fail(h, AMH_EINVAL, "amh_init: bad arguments");
   h->big_ready_C = -1;  // a kept proposal belongs to a state this call may overwrite
   h->ext_ready_C = -1;
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_init/hipSetDevice");
+  if (int rc = use_device(h, "amh_init")) return rc;
   amh::InitParams p{};
   p.out = *out;
   p.C = num_chains;
@@ -272,6 +401,7 @@ int amh_init(amh_handle* h, const uint32_t key[2], int64_t chain_offset, int64_t
   p.key1 = key[1];
   p.init_z = init_z;
   p.model = h->model;
+  hipError_t e;
   if (h->model_id == AMH_MODEL_EXTERNAL && p.d > 64) {
     e = amh::run_big_init(p, (hipStream_t)stream);  // pe0 = 0: the caller evaluates U(z0)
   } else if (amh::big_model(h->model_id, p.d)) {
@@ -296,15 +426,9 @@ int amh_init(amh_handle* h, const uint32_t key[2], int64_t chain_offset, int64_t
   return AMH_OK;
 }
 
-int amh_step(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out, int32_t n_steps,
-             const amh_collect* collect, void* stream) {
-  return amh_step_chained(h, num_chains, in, out, n_steps, collect, 0, stream);
-}
-
 int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out,
                      int32_t n_steps, const amh_collect* collect, int32_t flags, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_step: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_step: no model bound");
+  if (int rc = enter(h, "amh_step", true)) return rc;
   if (!state_ok(in) || !state_ok(out) || num_chains < 1 || n_steps < 0)
     return fail(h, AMH_EINVAL, "amh_step: bad arguments");
   if (h->model_id == AMH_MODEL_EXTERNAL)
@@ -314,266 +438,155 @@ int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, con
     return AMH_OK;
   }
   if (collect && collect->thinning < 1) return fail(h, AMH_EINVAL, "amh_step: thinning must be >= 1");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_step/hipSetDevice");
-  amh::StepParams p{};
-  p.in = *in;
-  p.out = *out;
-  p.C = num_chains;
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.eps = h->cfg.eps;
-  p.n_steps = n_steps;
-  p.thinning = collect ? collect->thinning : 1;
-  p.col_z = collect ? collect->z : nullptr;
-  p.col_pe = collect ? collect->potential_energy : nullptr;
-  p.accept_count = collect ? collect->accept_count : nullptr;
-  p.gamma_tab = h->gamma_tab;
-  p.gamma_tab_n = amh::kGammaTab;
-  p.model = h->model;
+  if (int rc = use_device(h, "amh_step")) return rc;
+  const amh::StepParams p = step_params(h, num_chains, *in, *out, n_steps, collect);
+  const int64_t C = num_chains;
+  const hipStream_t s = (hipStream_t)stream;
   if (amh::big_model(h->model_id, p.d)) {
     // d > 64: propose pass, MFMA potential, step pass per transition
-    const int64_t C = num_chains;
-    const size_t need = (size_t)C * (size_t)(4 * p.d + 1) * sizeof(float);
-    int rc = grow(h, &h->split_buf, &h->split_bytes, need, stream, "amh_step/hipMalloc");
-    if (rc != AMH_OK) return rc;
-    amh::BigParams q{};
-    q.out = *out;
-    q.C = C;
-    q.d = p.d;
-    q.W = p.W;
-    q.a = p.a;
-    q.target = p.target;
-    q.eps = p.eps;
-    q.gamma_tab = p.gamma_tab;
-    q.gamma_tab_n = p.gamma_tab_n;
-    q.xprop = h->split_buf;
-    q.wa = q.xprop + (size_t)C * p.d;
-    q.wr = q.wa + (size_t)C * p.d;
-    q.dg = q.wr + (size_t)C * p.d;
-    float* pep = q.dg + (size_t)C * p.d;
-    q.pep = pep;
-    q.accept_count = p.accept_count;
-    // the caller vouches (AMH_STEP_PROPOSAL_READY) that `in` is the unchanged
-    // output of the previous call, which kept its next proposal in the scratch
-    // (and `in` must be the very buffers that call wrote)
-    const bool ready = (flags & AMH_STEP_PROPOSAL_READY) && h->big_ready_C == C && same_buffers(*in, h->big_ready_out);
-    const bool keep_next = (flags & AMH_STEP_KEEP_PROPOSAL) != 0;
-    h->big_ready_C = -1;
-    for (int32_t t = 0; t < n_steps; ++t) {
-      q.in = (t == 0) ? *in : *out;
-      const bool keep = ((t + 1) % p.thinning) == 0;
-      const int64_t k = t / p.thinning;
-      q.col_z = (keep && p.col_z) ? p.col_z + (size_t)k * C * p.d : nullptr;
-      q.col_pe = (keep && p.col_pe) ? p.col_pe + (size_t)k * C : nullptr;
-      // the first transition's proposal comes from the propose pass (or the
-      // previous call); each step pass forms the next one on the fly, so the
-      // factor is read once per transition
-      if (t == 0 && !ready) e = amh::run_big_propose(q, (hipStream_t)stream);
-      if (e == hipSuccess) {
-        amh::PotParams pp{q.xprop, pep, C, p.d, h->model};
-        e = amh::run_big_potential(pp, (hipStream_t)stream);
-      }
-      if (e == hipSuccess) e = amh::run_big_step(q, (hipStream_t)stream, t + 1 < n_steps || keep_next);
-      if (e != hipSuccess) return hip_fail(h, e, "amh_step(d > 64)");
-    }
-    h->big_ready_C = keep_next ? C : -1;
-    h->big_ready_out = *out;
-    return AMH_OK;
+    amh::BigParams q = big_params(h, C, *in, *out, collect);
+    return run_chained(h, p, 4 * (size_t)p.d + 1, flags, stream, "amh_step(d > 64)",
+                       [&](const amh_state& from, Slot slot, bool propose, bool next) {
+                         q.xprop = h->split.as<float>();
+                         q.wa = q.xprop + (size_t)C * p.d;
+                         q.wr = q.wa + (size_t)C * p.d;
+                         q.dg = q.wr + (size_t)C * p.d;
+                         float* pep = q.dg + (size_t)C * p.d;
+                         q.pep = pep;
+                         q.in = from;
+                         q.col_z = slot.z;
+                         q.col_pe = slot.pe;
+                         hipError_t e = propose ? amh::run_big_propose(q, s) : hipSuccess;
+                         if (e == hipSuccess) {
+                           amh::PotParams pp{q.xprop, pep, C, p.d, h->model};
+                           e = amh::run_big_potential(pp, s);
+                         }
+                         if (e == hipSuccess) e = amh::run_big_step(q, s, next);
+                         return e;
+                       });
   }
   if (amh::split_model(h->model_id, p.d)) {
-    // one transition = propose, batched potential, step(U(z') from memory);
-    // collection is per launch: step t keeps slot t / thinning when (t+1) % thinning == 0
-    const int64_t C = num_chains;
-    const size_t need = (size_t)C * (size_t)(p.d + 1) * sizeof(float);
-    const bool grown = need > h->split_bytes;
-    int rc = grow(h, &h->split_buf, &h->split_bytes, need, stream, "amh_step/hipMalloc");
-    if (rc != AMH_OK) return rc;
-    // READY / KEEP as for d > 64: the step pass of each transition forms the
-    // next one's proposal (so the factor is read once per transition); only
-    // the first transition of a call may need the propose pass
-    const bool ready = !grown && (flags & AMH_STEP_PROPOSAL_READY) && h->big_ready_C == C &&
-                       same_buffers(*in, h->big_ready_out);
-    const bool keep_next = (flags & AMH_STEP_KEEP_PROPOSAL) != 0;
-    h->big_ready_C = -1;
-    float* xprop = h->split_buf;
-    float* peprop = h->split_buf + (size_t)C * p.d;
+    // one transition = propose, batched potential, step(U(z') from memory)
     amh::StepParams q = p;
     q.n_steps = 1;
     q.thinning = 1;
-    q.ext_pe = peprop;
-    q.ext_z = xprop;
-    for (int32_t t = 0; t < n_steps; ++t) {
-      q.in = (t == 0) ? *in : *out;
-      const bool keep = ((t + 1) % p.thinning) == 0;
-      const int64_t k = t / p.thinning;
-      q.col_z = (keep && p.col_z) ? p.col_z + (size_t)k * C * p.d : nullptr;
-      q.col_pe = (keep && p.col_pe) ? p.col_pe + (size_t)k * C : nullptr;
-      q.xprop_next = (t + 1 < n_steps || keep_next) ? xprop : nullptr;
-      if (t == 0 && !ready) e = amh::run_propose(q, xprop, (hipStream_t)stream);
-      if (e == hipSuccess) {
-        amh::PotParams pp{xprop, peprop, C, p.d, h->model, h->xpack};
-        e = amh::run_potential_lane(h->model_id, pp, (hipStream_t)stream);
-      }
-      if (e == hipSuccess) e = amh::run_step_ext(q, (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(h, e, "amh_step(split)");
-    }
-    h->big_ready_C = keep_next ? C : -1;
-    h->big_ready_out = *out;
-    return AMH_OK;
+    return run_chained(h, p, (size_t)p.d + 1, flags, stream, "amh_step(split)",
+                       [&](const amh_state& from, Slot slot, bool propose, bool next) {
+                         float* xprop = h->split.as<float>();
+                         float* peprop = xprop + (size_t)C * p.d;
+                         q.ext_z = xprop;
+                         q.ext_pe = peprop;
+                         q.in = from;
+                         q.col_z = slot.z;
+                         q.col_pe = slot.pe;
+                         q.xprop_next = next ? xprop : nullptr;
+                         hipError_t e = propose ? amh::run_propose(q, xprop, s) : hipSuccess;
+                         if (e == hipSuccess) {
+                           amh::PotParams pp{xprop, peprop, C, p.d, h->model, h->xpack};
+                           e = amh::run_potential_lane(h->model_id, pp, s);
+                         }
+                         if (e == hipSuccess) e = amh::run_step_ext(q, s);
+                         return e;
+                       });
   }
-  e = amh::run_step(h->model_id, p, (hipStream_t)stream);
+  const hipError_t e = amh::run_step(h->model_id, p, s);
   if (e != hipSuccess) return hip_fail(h, e, "amh_step");
   return AMH_OK;
 }
 
+int amh_step(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out, int32_t n_steps,
+             const amh_collect* collect, void* stream) {
+  return amh_step_chained(h, num_chains, in, out, n_steps, collect, 0, stream);
+}
+
 int amh_potential(amh_handle* h, const float* z, float* pe, int64_t n, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_potential: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_potential: no model bound");
+  if (int rc = enter(h, "amh_potential", true)) return rc;
   if (!z || !pe || n < 1) return fail(h, AMH_EINVAL, "amh_potential: bad arguments");
   if (h->model_id == AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, "amh_potential: the potential is external");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_potential/hipSetDevice");
+  if (int rc = use_device(h, "amh_potential")) return rc;
   amh::PotParams p{z, pe, n, h->cfg.dim, h->model, h->xpack};
-  e = amh::big_model(h->model_id, p.d)     ? amh::run_big_potential(p, (hipStream_t)stream)
-      : amh::split_model(h->model_id, p.d) ? amh::run_potential_lane(h->model_id, p, (hipStream_t)stream)
-                                           : amh::run_potential(h->model_id, p, (hipStream_t)stream);
+  const hipError_t e = amh::big_model(h->model_id, p.d) ? amh::run_big_potential(p, (hipStream_t)stream)
+                       : amh::split_model(h->model_id, p.d)
+                           ? amh::run_potential_lane(h->model_id, p, (hipStream_t)stream)
+                           : amh::run_potential(h->model_id, p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "amh_potential");
   return AMH_OK;
 }
 
-// ------------------------------------------------- external potential --
+int amh_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, int64_t n_points, int64_t n_samples,
+                   const float* loc, const float* scale_packed, float log_step_size, int32_t n, float* out,
+                   void* stream) {
+  (void)loc;  // the frozen kernel's proposal does not read the mean (arwmh.py:166-167)
+  if (int rc = enter(h, "amh_sample_pnx", true)) return rc;
+  if (!key || !x || !scale_packed || !out || n_points < 1 || n_samples < 1 || n < 0)
+    return fail(h, AMH_EINVAL, "amh_sample_pnx: bad arguments");
+  if (h->cfg.dim > 64 && !amh::big_model(h->model_id, h->cfg.dim))
+    return fail(h, AMH_EINVAL, "amh_sample_pnx: d > 64 needs the dense Gaussian (d <= 256)");
+  if (h->model_id == AMH_MODEL_EXTERNAL)
+    return fail(h, AMH_EINVAL, "amh_sample_pnx: an external potential runs through amh_pnx_propose / amh_pnx_accept");
+  if (int rc = use_device(h, "amh_sample_pnx")) return rc;
+  amh::PnxParams p{};
+  p.x = x;
+  p.n_points = n_points;
+  p.n_samples = n_samples;
+  p.scale = scale_packed;
+  p.log_step_size = log_step_size;
+  p.eps = h->cfg.eps;
+  p.n = n;
+  p.d = h->cfg.dim;
+  p.key0 = key[0];
+  p.key1 = key[1];
+  p.out = out;
+  p.model = h->model;
+  const hipError_t e =
+      (p.d > 64) ? amh::run_big_pnx(p, (hipStream_t)stream) : amh::run_pnx(h->model_id, p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_sample_pnx");
+  return AMH_OK;
+}
+
+int amh_chain_keys(const uint32_t key[2], int64_t chain_offset, int64_t n, uint32_t* out, void* stream) {
+  if (!key || !out || n < 1 || chain_offset < 0) return fail(nullptr, AMH_EINVAL, "amh_chain_keys: bad arguments");
+  hipError_t e = amh::run_chain_keys(key[0], key[1], chain_offset, n, out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_chain_keys");
+  return AMH_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------ external potential --
 // AMH_MODEL_EXTERNAL: the split transition (amh_split.hip propose_kernel,
 // the step kernel with U(z') read from memory -- the diamonds path's two
 // launches) with the caller's U in between.
-static amh::StepParams ext_params(amh_handle* h, int64_t C, const amh_state* in, const amh_state* out) {
-  amh::StepParams p{};
-  p.in = *in;
-  p.out = *out;
-  p.C = C;
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.eps = h->cfg.eps;
-  p.n_steps = 1;
-  p.thinning = 1;
-  p.gamma_tab = h->gamma_tab;
-  p.gamma_tab_n = amh::kGammaTab;
-  p.model = h->model;
-  return p;
-}
+namespace {
 
 // d > 64: big_propose_kernel / big_step_kernel with the caller's U(z'); the
 // proposals live in the caller's zprop, the solves (wa, wr) and the diagonal
 // in the handle's scratch, tied to the state they were formed from
-static int ext_big_params(amh_handle* h, int64_t C, const amh_state* in, const amh_state* out, float* zprop,
-                          void* stream, amh::BigParams* q) {
+int ext_big_params(amh_handle* h, int64_t C, const amh_state* in, const amh_state* out, float* zprop,
+                   const amh_collect* collect, void* stream, amh::BigParams* q) {
   const int d = h->cfg.dim;
   const size_t need = (size_t)C * (size_t)(3 * d) * sizeof(float);
-  const bool grown = need > h->split_bytes;
-  int rc = grow(h, &h->split_buf, &h->split_bytes, need, stream, "amh_propose/hipMalloc");
-  if (rc != AMH_OK) return rc;
+  const bool grown = need > h->split.bytes;
+  if (int rc = h->split.grow(h, need, stream, "amh_propose")) return rc;
   if (grown) h->ext_ready_C = -1;
   h->big_ready_C = -1;  // the scratch now holds the external path's solves
-  *q = amh::BigParams{};
-  q->in = *in;
-  q->out = *out;
-  q->C = C;
-  q->d = d;
-  q->W = h->cfg.num_warmup;
-  q->a = h->cfg.lr_decay;
-  q->target = h->cfg.target_accept_prob;
-  q->eps = h->cfg.eps;
-  q->gamma_tab = h->gamma_tab;
-  q->gamma_tab_n = amh::kGammaTab;
+  *q = big_params(h, C, *in, *out, collect);
   q->xprop = zprop;
-  q->wa = h->split_buf;
+  q->wa = h->split.as<float>();
   q->wr = q->wa + (size_t)C * d;
   q->dg = q->wr + (size_t)C * d;
   return AMH_OK;
 }
 
-int amh_propose(amh_handle* h, int64_t num_chains, const amh_state* in, float* zprop, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_propose: null handle");
-  if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, "amh_propose: needs AMH_MODEL_EXTERNAL");
-  if (!state_ok(in) || !zprop || num_chains < 1) return fail(h, AMH_EINVAL, "amh_propose: bad arguments");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_propose/hipSetDevice");
-  if (h->cfg.dim > 64) {
-    amh::BigParams q;
-    int rc = ext_big_params(h, num_chains, in, in, zprop, stream, &q);
-    if (rc != AMH_OK) return rc;
-    e = amh::run_big_propose(q, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(h, e, "amh_propose(d > 64)");
-    h->ext_ready_C = num_chains;
-    h->ext_ready_in = *in;
-    return AMH_OK;
-  }
-  const amh::StepParams p = ext_params(h, num_chains, in, in);
-  e = amh::run_propose(p, zprop, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_propose");
-  return AMH_OK;
-}
-
-int amh_step_external(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out,
-                      const float* zprop, const float* pe_prop, float* zprop_next, const amh_collect* collect,
-                      void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_step_external: null handle");
-  if (h->model_id != AMH_MODEL_EXTERNAL)
-    return fail(h, AMH_EINVAL, "amh_step_external: needs AMH_MODEL_EXTERNAL");
-  if (!state_ok(in) || !state_ok(out) || !zprop || !pe_prop || num_chains < 1)
-    return fail(h, AMH_EINVAL, "amh_step_external: bad arguments");
-  if (collect && collect->thinning != 1) return fail(h, AMH_EINVAL, "amh_step_external: thinning must be 1");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_step_external/hipSetDevice");
-  if (h->cfg.dim > 64) {
-    // the step pass reads the solves amh_propose (or the previous step) formed
-    // for exactly this state, and writes the next proposals in place
-    if (h->ext_ready_C != num_chains || !same_buffers(*in, h->ext_ready_in))
-      return fail(h, AMH_EINVAL, "amh_step_external: d > 64 needs the proposals of this state (amh_propose first)");
-    if (zprop_next && zprop_next != zprop)
-      return fail(h, AMH_EINVAL, "amh_step_external: d > 64 forms the next proposals in place (zprop_next == zprop)");
-    amh::BigParams q;
-    int rc = ext_big_params(h, num_chains, in, out, const_cast<float*>(zprop), stream, &q);
-    if (rc != AMH_OK) return rc;
-    q.pep = pe_prop;
-    q.accept_count = collect ? collect->accept_count : nullptr;
-    q.col_z = collect ? collect->z : nullptr;
-    q.col_pe = collect ? collect->potential_energy : nullptr;
-    h->ext_ready_C = -1;
-    e = amh::run_big_step(q, (hipStream_t)stream, zprop_next != nullptr);
-    if (e != hipSuccess) return hip_fail(h, e, "amh_step_external(d > 64)");
-    if (zprop_next) {
-      h->ext_ready_C = num_chains;
-      h->ext_ready_in = *out;
-    }
-    return AMH_OK;
-  }
-  amh::StepParams p = ext_params(h, num_chains, in, out);
-  p.col_z = collect ? collect->z : nullptr;
-  p.col_pe = collect ? collect->potential_energy : nullptr;
-  p.accept_count = collect ? collect->accept_count : nullptr;
-  p.ext_z = zprop;
-  p.ext_pe = pe_prop;
-  p.xprop_next = zprop_next;
-  e = amh::run_step_ext(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_step_external");
-  return AMH_OK;
-}
-
-static int pnx_ext(amh_handle* h, const uint32_t key[2], float* z, float* pe, int64_t C, const float* scale,
-                   float lam, int32_t t, float* zprop, const float* pe_prop, bool accept, void* stream,
-                   const char* who) {
-  if (!h) return fail(nullptr, AMH_EINVAL, std::string(who) + ": null handle");
+// sample_Pnx around the caller's potential (d <= 64): the propose or the accept pass of step t
+int pnx_ext(amh_handle* h, const uint32_t key[2], float* z, float* pe, int64_t C, const float* scale, float lam,
+            int32_t t, float* zprop, const float* pe_prop, bool accept, void* stream, const char* who) {
+  if (int rc = enter(h, who, false)) return rc;
   if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, std::string(who) + ": needs AMH_MODEL_EXTERNAL");
   if (h->cfg.dim > 64) return fail(h, AMH_EINVAL, std::string(who) + ": an external sample_Pnx needs d <= 64");
   if (!key || !z || !zprop || C < 1 || t < 0 || (accept ? (!pe || !pe_prop) : !scale))
     return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, (std::string(who) + "/hipSetDevice").c_str());
+  if (int rc = use_device(h, who)) return rc;
   amh::PnxExtParams p{};
   p.z = z;
   p.pe = pe;
@@ -587,8 +600,70 @@ static int pnx_ext(amh_handle* h, const uint32_t key[2], float* z, float* pe, in
   p.d = h->cfg.dim;
   p.key0 = key[0];
   p.key1 = key[1];
-  e = amh::run_pnx_ext(p, accept, (hipStream_t)stream);
+  const hipError_t e = amh::run_pnx_ext(p, accept, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amh_propose(amh_handle* h, int64_t num_chains, const amh_state* in, float* zprop, void* stream) {
+  if (int rc = enter(h, "amh_propose", false)) return rc;
+  if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, "amh_propose: needs AMH_MODEL_EXTERNAL");
+  if (!state_ok(in) || !zprop || num_chains < 1) return fail(h, AMH_EINVAL, "amh_propose: bad arguments");
+  if (int rc = use_device(h, "amh_propose")) return rc;
+  if (h->cfg.dim > 64) {
+    amh::BigParams q;
+    if (int rc = ext_big_params(h, num_chains, in, in, zprop, nullptr, stream, &q)) return rc;
+    const hipError_t e = amh::run_big_propose(q, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, "amh_propose(d > 64)");
+    h->ext_ready_C = num_chains;
+    h->ext_ready_in = *in;
+    return AMH_OK;
+  }
+  const amh::StepParams p = step_params(h, num_chains, *in, *in, 1, nullptr);
+  const hipError_t e = amh::run_propose(p, zprop, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_propose");
+  return AMH_OK;
+}
+
+int amh_step_external(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out,
+                      const float* zprop, const float* pe_prop, float* zprop_next, const amh_collect* collect,
+                      void* stream) {
+  if (int rc = enter(h, "amh_step_external", false)) return rc;
+  if (h->model_id != AMH_MODEL_EXTERNAL)
+    return fail(h, AMH_EINVAL, "amh_step_external: needs AMH_MODEL_EXTERNAL");
+  if (!state_ok(in) || !state_ok(out) || !zprop || !pe_prop || num_chains < 1)
+    return fail(h, AMH_EINVAL, "amh_step_external: bad arguments");
+  if (collect && collect->thinning != 1) return fail(h, AMH_EINVAL, "amh_step_external: thinning must be 1");
+  if (int rc = use_device(h, "amh_step_external")) return rc;
+  if (h->cfg.dim > 64) {
+    // the step pass reads the solves amh_propose (or the previous step) formed
+    // for exactly this state, and writes the next proposals in place
+    if (h->ext_ready_C != num_chains || !same_buffers(*in, h->ext_ready_in))
+      return fail(h, AMH_EINVAL, "amh_step_external: d > 64 needs the proposals of this state (amh_propose first)");
+    if (zprop_next && zprop_next != zprop)
+      return fail(h, AMH_EINVAL, "amh_step_external: d > 64 forms the next proposals in place (zprop_next == zprop)");
+    amh::BigParams q;
+    if (int rc = ext_big_params(h, num_chains, in, out, const_cast<float*>(zprop), collect, stream, &q)) return rc;
+    q.pep = pe_prop;
+    h->ext_ready_C = -1;
+    const hipError_t e = amh::run_big_step(q, (hipStream_t)stream, zprop_next != nullptr);
+    if (e != hipSuccess) return hip_fail(h, e, "amh_step_external(d > 64)");
+    if (zprop_next) {
+      h->ext_ready_C = num_chains;
+      h->ext_ready_in = *out;
+    }
+    return AMH_OK;
+  }
+  amh::StepParams p = step_params(h, num_chains, *in, *out, 1, collect);
+  p.ext_z = zprop;
+  p.ext_pe = pe_prop;
+  p.xprop_next = zprop_next;
+  const hipError_t e = amh::run_step_ext(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_step_external");
   return AMH_OK;
 }
 
@@ -604,54 +679,22 @@ int amh_pnx_accept(amh_handle* h, const uint32_t key[2], float* z, float* pe, in
                  "amh_pnx_accept");
 }
 
-int amh_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, int64_t n_points, int64_t n_samples,
-                   const float* loc, const float* scale_packed, float log_step_size, int32_t n, float* out,
-                   void* stream) {
-  (void)loc;  // the frozen kernel's proposal does not read the mean (arwmh.py:166-167)
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_sample_pnx: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_sample_pnx: no model bound");
-  if (!key || !x || !scale_packed || !out || n_points < 1 || n_samples < 1 || n < 0)
-    return fail(h, AMH_EINVAL, "amh_sample_pnx: bad arguments");
-  if (h->cfg.dim > 64 && !amh::big_model(h->model_id, h->cfg.dim))
-    return fail(h, AMH_EINVAL, "amh_sample_pnx: d > 64 needs the dense Gaussian (d <= 256)");
-  if (h->model_id == AMH_MODEL_EXTERNAL)
-    return fail(h, AMH_EINVAL, "amh_sample_pnx: an external potential runs through amh_pnx_propose / amh_pnx_accept");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_sample_pnx/hipSetDevice");
-  amh::PnxParams p{};
-  p.x = x;
-  p.n_points = n_points;
-  p.n_samples = n_samples;
-  p.scale = scale_packed;
-  p.log_step_size = log_step_size;
-  p.eps = h->cfg.eps;
-  p.n = n;
-  p.d = h->cfg.dim;
-  p.key0 = key[0];
-  p.key1 = key[1];
-  p.out = out;
-  p.model = h->model;
-  e = (p.d > 64) ? amh::run_big_pnx(p, (hipStream_t)stream) : amh::run_pnx(h->model_id, p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_sample_pnx");
-  return AMH_OK;
-}
-
-int amh_chain_keys(const uint32_t key[2], int64_t chain_offset, int64_t n, uint32_t* out, void* stream) {
-  if (!key || !out || n < 1 || chain_offset < 0) return fail(nullptr, AMH_EINVAL, "amh_chain_keys: bad arguments");
-  hipError_t e = amh::run_chain_keys(key[0], key[1], chain_offset, n, out, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_chain_keys");
-  return AMH_OK;
-}
+}  // extern "C"
 
 // -------------------------------------------------------------------- ASSS --
-static bool asss_state_ok(const amh_state* s) {
+namespace {
+
+bool asss_state_ok(const amh_state* s) {
   return s && s->i && s->z && s->potential_energy && s->loc && s->scale && s->as_change && s->rng_key;
 }
 
+}  // namespace
+
+extern "C" {
+
 int amh_asss_step(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out, int32_t n_steps,
                   const amh_collect* collect, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_asss_step: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_asss_step: no model bound");
+  if (int rc = enter(h, "amh_asss_step", true)) return rc;
   if (!asss_state_ok(in) || !asss_state_ok(out) || num_chains < 1 || n_steps < 0)
     return fail(h, AMH_EINVAL, "amh_asss_step: bad arguments");
   const bool big = amh::big_model(h->model_id, h->cfg.dim);
@@ -661,51 +704,32 @@ int amh_asss_step(amh_handle* h, int64_t num_chains, const amh_state* in, const 
     return fail(h, AMH_EINVAL, "amh_asss_step: the slice sampler needs a device potential (not external)");
   if (collect && collect->thinning < 1) return fail(h, AMH_EINVAL, "amh_asss_step: thinning must be >= 1");
   if (n_steps == 0) return AMH_OK;
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_asss_step/hipSetDevice");
-  amh::StepParams p{};
-  p.in = *in;
-  p.out = *out;
-  p.C = num_chains;
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.eps = h->cfg.eps;
-  p.n_steps = n_steps;
-  p.thinning = collect ? collect->thinning : 1;
-  p.col_z = collect ? collect->z : nullptr;
-  p.col_pe = collect ? collect->potential_energy : nullptr;
+  if (int rc = use_device(h, "amh_asss_step")) return rc;
+  amh::StepParams p = step_params(h, num_chains, *in, *out, n_steps, collect);
   p.accept_count = nullptr;
-  p.gamma_tab = h->gamma_tab;
-  p.gamma_tab_n = amh::kGammaTab;
-  p.model = h->model;
   if (big) {
     // large d: one launch per transition (the factor streamed four times),
     // the first from `in`, the rest in place on `out`
-    const int64_t keep_stride = num_chains * (int64_t)h->cfg.dim;
     for (int32_t t = 0; t < n_steps; ++t) {
       amh::StepParams q = p;
       if (t > 0) q.in = *out;
       q.n_steps = 1;
-      const bool keep = (t + 1) % p.thinning == 0;
-      const int64_t k = (t + 1) / p.thinning - 1;
-      q.col_z = (keep && p.col_z) ? p.col_z + k * keep_stride : nullptr;
-      q.col_pe = (keep && p.col_pe) ? p.col_pe + k * num_chains : nullptr;
-      e = amh::run_asss_big_step(q, (hipStream_t)stream);
+      const Slot slot = collect_slot(p, t);
+      q.col_z = slot.z;
+      q.col_pe = slot.pe;
+      const hipError_t e = amh::run_asss_big_step(q, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(h, e, "amh_asss_step(large d)");
     }
     return AMH_OK;
   }
-  e = amh::run_asss_step(h->model_id, p, (hipStream_t)stream);
+  const hipError_t e = amh::run_asss_step(h->model_id, p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "amh_asss_step");
   return AMH_OK;
 }
 
 int amh_asss_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, int64_t n_points, int64_t n_samples,
                         const float* loc, const float* scale_packed, int32_t n, float* out, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_asss_sample_pnx: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_asss_sample_pnx: no model bound");
+  if (int rc = enter(h, "amh_asss_sample_pnx", true)) return rc;
   if (!key || !x || !loc || !scale_packed || !out || n_points < 1 || n_samples < 1 || n < 0)
     return fail(h, AMH_EINVAL, "amh_asss_sample_pnx: bad arguments");
   const bool big = amh::big_model(h->model_id, h->cfg.dim);
@@ -713,8 +737,7 @@ int amh_asss_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, in
     return fail(h, AMH_EINVAL, "amh_asss_sample_pnx: dim must be <= 64, or a dense Gaussian up to 256");
   if (h->model_id == AMH_MODEL_EXTERNAL)
     return fail(h, AMH_EINVAL, "amh_asss_sample_pnx: the slice sampler needs a device potential (not external)");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_asss_sample_pnx/hipSetDevice");
+  if (int rc = use_device(h, "amh_asss_sample_pnx")) return rc;
   amh::AsssPnxParams p{};
   p.x = x;
   p.n_points = n_points;
@@ -728,12 +751,17 @@ int amh_asss_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, in
   p.key1 = key[1];
   p.out = out;
   p.model = h->model;
-  e = big ? amh::run_asss_big_pnx(p, (hipStream_t)stream) : amh::run_asss_pnx(h->model_id, p, (hipStream_t)stream);
+  const hipError_t e =
+      big ? amh::run_asss_big_pnx(p, (hipStream_t)stream) : amh::run_asss_pnx(h->model_id, p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "amh_asss_sample_pnx");
   return AMH_OK;
 }
 
+}  // extern "C"
+
 // -------------------------------------------------------------- evaluation --
+extern "C" {
+
 int64_t amh_kernel_sum_scratch(int64_t n, int64_t m) { return n > 0 && m > 0 ? amh::kernel_sum_blocks(n, m) : 0; }
 
 int amh_kernel_sum(const float* a, int64_t n, const float* b, int64_t m, int32_t d, float gamma, int32_t skip_diag,
@@ -769,65 +797,38 @@ int amh_normals(const uint32_t key[2], int64_t n, float* out, void* stream) {
   return AMH_OK;
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------- pooled covariance --
-static bool pooled_ok(const amh_pooled_state* s) {
+namespace {
+
+bool pooled_ok(const amh_pooled_state* s) {
   return s && s->i && s->z && s->potential_energy && s->rng_key && s->mean_accept_prob && s->loc && s->scale &&
          s->log_step_size && s->as_change && s->cov;
 }
 
-int amh_pooled_sums_size(int32_t dim, int64_t* v) {
-  if (dim < 1 || dim > 256 || !v) return fail(nullptr, AMH_EINVAL, "amh_pooled_sums_size: bad arguments");
-  *v = (int64_t)dim + (int64_t)dim * (dim + 1) / 2 + 2;
-  return AMH_OK;
+// the handle's chunk-partial scratch: n_chunks rows plus the reduction's group
+// sums, a row being the sums themselves or, at d >= 64 (`big`), their tile layout
+int reserve_partials(amh_handle* h, int64_t n_chunks, bool big, void* stream, const char* who) {
+  const int64_t vrow = big ? amh::pooled_big_tile_V(h->cfg.dim) : amh::pooled_sums_len(h->cfg.dim);
+  return h->partials.grow(h, (size_t)amh::pooled_scratch_rows(n_chunks) * (size_t)vrow * sizeof(double), stream, who);
 }
 
-}  // extern "C"
-
-// prep_for_update: the update follows in the same library call with no
-// exchange in between (amh_pooled_step_k on one rank), so the large-d
-// reduction's last kernel also forms that update's Sigma'
-// A/B switches of the diagnostic build only (-DAMH_DIAG, `make stamps`; the
-// bits are the same either way, the release library reads no environment):
-// AMH_POOLED_FUSED_REDUCE=0 keeps the d = 64 reduction in its own launch;
-// AMH_POOLED_NOISE_AHEAD=0 draws no noise ahead (each stats kernel draws its own)
-static bool reduce_fusion_off() {
-#ifdef AMH_DIAG
-  static const bool off = [] {
-    const char* e = getenv("AMH_POOLED_FUSED_REDUCE");
-    return e != nullptr && e[0] == '0';
-  }();
-  return off;
-#else
-  return false;
-#endif
+// d >= 64: the update's staging; the post kernel's arrival ticket in it starts
+// at zero (its last block resets it)
+int reserve_update_scratch(amh_handle* h, void* stream, const char* who) {
+  return h->upd.grow(h, amh::pooled_update_scratch_floats(h->cfg.dim) * sizeof(float), stream, who, true);
 }
 
-static bool noise_ahead_off() {
-#ifdef AMH_DIAG
-  static const bool off = [] {
-    const char* e = getenv("AMH_POOLED_NOISE_AHEAD");
-    return e != nullptr && e[0] == '0';
-  }();
-  return off;
-#else
-  return false;
-#endif
-}
-
-// the handle's chunk-partial scratch for n_chunks rows of vrow entries plus
-// the reduction's group sums (grown, never shrunk)
-static int grow_partials(amh_handle* h, int64_t n_chunks, int64_t vrow, void* stream, const char* where) {
-  const size_t need = (size_t)amh::pooled_scratch_rows(n_chunks) * (size_t)vrow * sizeof(double);
-  if (need <= h->partials_bytes) return AMH_OK;
-  if (h->partials) {
-    (void)hipStreamSynchronize((hipStream_t)stream);  // a queued launch may still use the old scratch
-    (void)hipFree(h->partials);
-  }
-  h->partials = nullptr;
-  h->partials_bytes = 0;
-  hipError_t e = hipMalloc(&h->partials, need);
-  if (e != hipSuccess) return hip_fail(h, e, where);
-  h->partials_bytes = need;
+// d >= 64: room for the noise the update launch draws ahead for C chains; the
+// records of a new buffer say i = -1, which matches no chain
+int reserve_noise(amh_handle* h, int64_t C, void* stream, const char* who) {
+  const size_t need = (size_t)C * amh::noise_row_bytes(h->cfg.dim);
+  if (need <= h->noise.bytes) return AMH_OK;
+  if (int rc = h->noise.grow(h, need, stream, who)) return rc;
+  h->noise_cap = C;
+  const hipError_t e = hipMemsetAsync(h->noise.ptr, 0xFF, (size_t)C * amh::kNoiseRecordBytes, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipMemsetAsync");
   return AMH_OK;
 }
 
@@ -840,18 +841,20 @@ struct DeferredReduce {
   int32_t accumulate = 0;
 };
 
-static int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
-                             float* z_out, float* pe_out, double* sums, void* stream, bool prep_for_update,
-                             bool* sigma_ready, DeferredReduce* deferred = nullptr, bool pack_ready = false) {
+// prep_for_update: the update follows in the same library call with no
+// exchange in between (amh_pooled_step_k on one rank), so the large-d
+// reduction's last kernel also forms that update's Sigma'
+int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps, float* z_out,
+                      float* pe_out, double* sums, void* stream, bool prep_for_update, bool* sigma_ready,
+                      DeferredReduce* deferred = nullptr, bool pack_ready = false) {
+  const char* const who = "amh_pooled_stats";
   if (sigma_ready) *sigma_ready = false;
   if (deferred) *deferred = DeferredReduce{};
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_pooled_stats: null handle");
-  if (!h->model_id) return fail(h, AMH_ENOMODEL, "amh_pooled_stats: no model bound");
+  if (int rc = enter(h, who, true)) return rc;
   if (!pooled_ok(in) || !z_out || !pe_out || !sums || num_chains < 1 || k_steps < 1)
     return fail(h, AMH_EINVAL, "amh_pooled_stats: bad arguments");
   if (int rc = check_device_flag(h)) return rc;
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats/hipSetDevice");
+  if (int rc = use_device(h, who)) return rc;
   const int d = h->cfg.dim;
   const bool big = amh::pooled_big_model(h->model_id, d);
   if (d > 64 && !big) return fail(h, AMH_EINVAL, "amh_pooled_stats: d > 64 needs d % 32 == 0 in the pooled mode");
@@ -860,8 +863,7 @@ static int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled
   const int cpw = amh::pooled_cpw(num_chains);
   const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
   const int64_t n_chunks = big ? amh::pooled_big_chunks(num_chains, d) : (num_chains + chunk - 1) / chunk;
-  const int64_t vrow = big ? amh::pooled_big_tile_V(d) : d + (int64_t)d * (d + 1) / 2 + 2;
-  if (int rc = grow_partials(h, n_chunks, vrow, stream, "amh_pooled_stats/hipMalloc")) return rc;
+  if (int rc = reserve_partials(h, n_chunks, big, stream, who)) return rc;
   amh::PooledStatsParams p{};
   p.C = num_chains;
   p.d = d;
@@ -875,113 +877,132 @@ static int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled
   p.eps = h->cfg.eps;
   p.z_out = z_out;
   p.pe_out = pe_out;
-  p.partials = h->partials;
+  p.partials = h->partials.as<double>();
   p.model = h->model;
   p.k_steps = k_steps;
-  if (big) {
-    // xprop + U(xprop) of the unfused path, or the fused path's A-operand copies
-    const size_t nb = ((size_t)num_chains * (size_t)(d + 1) + (size_t)amh::pooled_big_pack_floats(d)) * sizeof(float);
-    h->big_ready_C = -1;
-    void* const split_was = h->split_buf;
-    int rc = grow(h, &h->split_buf, &h->split_bytes, nb, stream, "amh_pooled_stats/hipMalloc");
-    if (rc != AMH_OK) return rc;
-    // the copies are current only when the previous update of this call wrote
-    // them into this very buffer (amh_pooled_step_k; d > 64 fused path)
-    p.pack_ready = (pack_ready && d != 64 && h->split_buf == split_was) ? 1 : 0;
-    {
-      // noise drawn ahead by the update launch (records checked per chain
-      // by the stats kernel, so a stale or foreign buffer is never used)
-      const size_t nn = (size_t)num_chains * (16 + (size_t)d * sizeof(float));
-      if (nn > h->noise_bytes) {
-        rc = grow(h, &h->noise_buf, &h->noise_bytes, nn, stream, "amh_pooled_stats/hipMalloc");
-        if (rc != AMH_OK) return rc;
-        h->noise_cap = num_chains;
-        e = hipMemsetAsync(h->noise_buf, 0xFF, (size_t)num_chains * 16, (hipStream_t)stream);  // i = -1: no match
-        if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats/hipMemsetAsync");
-      }
-      p.xrec = (const uint4*)h->noise_buf;
-      p.xi = h->noise_buf + 4 * h->noise_cap;
-      p.xi_cap = h->noise_cap;
-      h->noise_C = num_chains;
-      h->noise_keys = in->rng_key;
-      if (prep_for_update) {  // grown here: pooled_update_impl's grow is then a no-op
-        const size_t un = ((size_t)d * (d + 4) / 2 + 8 + (size_t)d) * sizeof(float);
-        const bool fresh = un > h->upd_bytes;
-        rc = grow(h, &h->upd_buf, &h->upd_bytes, un, stream, "amh_pooled_stats/hipMalloc");
-        if (rc != AMH_OK) return rc;
-        if (fresh) {
-          e = hipMemsetAsync(h->upd_buf, 0, h->upd_bytes, (hipStream_t)stream);
-          if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats/hipMemsetAsync");
-        }
-      }
-    }
-    // one launch sequence per step of the block, the sums accumulated; d = 64:
-    // the block's K steps in one launch (pooled_fused64_kernel, p.k_steps)
-    const int32_t n_launch = (d == 64) ? 1 : k_steps;
-    for (int32_t t0 = 0; t0 < n_launch; ++t0) {
-      const int32_t t = (d == 64) ? k_steps - 1 : t0;  // the step the launch ends with
-      p.i_add = (d == 64) ? 0 : t;
-      p.accumulate = (d == 64) ? 0 : t > 0;
-      if (prep_for_update && d != 64 && t == k_steps - 1) {
-        p.prep.cov = in->cov;
-        p.prep.i = in->i;
-        p.prep.scratch = h->upd_buf;
-        p.prep.N = (double)num_chains * (double)k_steps;
-        p.prep.W = h->cfg.num_warmup;
-        p.prep.K = k_steps;
-        p.prep.a = h->cfg.lr_decay;
-        if (sigma_ready) *sigma_ready = true;
-      }
-      if (t0 > 0) {
-        p.z = z_out;
-        p.pe = pe_out;
-      }
-      p.defer_reduce = (prep_for_update && deferred && d == 64 && t == k_steps - 1 && !reduce_fusion_off()) ? 1 : 0;
-      if (p.defer_reduce) {
-        deferred->partials = (const float*)h->partials;
-        deferred->n_chunks = n_chunks;
-        deferred->accumulate = p.accumulate;
-      }
-      e = amh::run_pooled_big_stats(p, h->split_buf, h->split_buf + (size_t)num_chains * d, sums,
-                                    (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats(MFMA path)");
-      p.pack_ready = 1;  // the K steps of a pooled block share the frozen factor
-    }
+  if (!big) {
+    const hipError_t e = amh::run_pooled_stats(h->model_id, p, sums, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats");
     return AMH_OK;
   }
-  e = amh::run_pooled_stats(h->model_id, p, sums, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats");
+  // the fused path's A-operand copies
+  h->big_ready_C = -1;
+  void* const split_was = h->split.ptr;
+  if (int rc = h->split.grow(h, (size_t)amh::pooled_big_pack_floats(d) * sizeof(float), stream, who)) return rc;
+  // the copies are current only when the previous update of this call wrote
+  // them into this very buffer (amh_pooled_step_k; d > 64 fused path)
+  p.pack_ready = (pack_ready && d != 64 && h->split.ptr == split_was) ? 1 : 0;
+  // noise drawn ahead by the update launch (records checked per chain
+  // by the stats kernel, so a stale or foreign buffer is never used)
+  if (int rc = reserve_noise(h, num_chains, stream, who)) return rc;
+  p.xrec = h->noise.as<const uint4>();
+  p.xi = amh::noise_xi(h->noise.as<float>(), h->noise_cap);
+  p.xi_cap = h->noise_cap;
+  h->noise_C = num_chains;
+  h->noise_keys = in->rng_key;
+  if (prep_for_update)  // grown here: pooled_update_impl's grow is then a no-op
+    if (int rc = reserve_update_scratch(h, stream, who)) return rc;
+  // one launch sequence per step of the block, the sums accumulated; d = 64:
+  // the block's K steps in one launch (pooled_fused64_kernel, p.k_steps)
+  const int32_t n_launch = (d == 64) ? 1 : k_steps;
+  for (int32_t t0 = 0; t0 < n_launch; ++t0) {
+    const int32_t t = (d == 64) ? k_steps - 1 : t0;  // the step the launch ends with
+    p.i_add = (d == 64) ? 0 : t;
+    p.accumulate = (d == 64) ? 0 : t > 0;
+    if (prep_for_update && d != 64 && t == k_steps - 1) {
+      p.prep.cov = in->cov;
+      p.prep.i = in->i;
+      p.prep.scratch = h->upd.as<float>();
+      p.prep.N = (double)num_chains * (double)k_steps;
+      p.prep.W = h->cfg.num_warmup;
+      p.prep.K = k_steps;
+      p.prep.a = h->cfg.lr_decay;
+      if (sigma_ready) *sigma_ready = true;
+    }
+    if (t0 > 0) {
+      p.z = z_out;
+      p.pe = pe_out;
+    }
+    p.defer_reduce = (prep_for_update && deferred && d == 64 && t == k_steps - 1 &&
+                      !diag_env_off("AMH_POOLED_FUSED_REDUCE"))  // =0 keeps the d = 64 reduction in its own launch
+                         ? 1
+                         : 0;
+    if (p.defer_reduce) {
+      deferred->partials = h->partials.as<const float>();
+      deferred->n_chunks = n_chunks;
+      deferred->accumulate = p.accumulate;
+    }
+    const hipError_t e = amh::run_pooled_big_stats(p, h->split.as<float>(), sums, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats(MFMA path)");
+    p.pack_ready = 1;  // the K steps of a pooled block share the frozen factor
+  }
   return AMH_OK;
 }
 
-static int pooled_update_impl(amh_handle* h, const double* sums, const amh_pooled_state* in,
-                              const amh_pooled_state* out, int32_t k_steps, void* stream, bool sigma_ready,
-                              const DeferredReduce* deferred = nullptr, float* pack_out = nullptr);
-
-extern "C" {
-
-int amh_pooled_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
-                       float* z_out, float* pe_out, double* sums, void* stream) {
-  return pooled_stats_impl(h, num_chains, in, k_steps, z_out, pe_out, sums, stream, false, nullptr);
-}
-
-int amh_pooled_stats(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, float* z_out, float* pe_out,
-                     double* sums, void* stream) {
-  return amh_pooled_stats_k(h, num_chains, in, 1, z_out, pe_out, sums, stream);
-}
-
-int amh_pooled_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in, const amh_pooled_state* out,
-                        int32_t k_steps, void* stream) {
-  return pooled_update_impl(h, sums, in, out, k_steps, stream, false);
+int pooled_update_impl(amh_handle* h, const double* sums, const amh_pooled_state* in, const amh_pooled_state* out,
+                       int32_t k_steps, void* stream, bool sigma_ready, const DeferredReduce* deferred = nullptr,
+                       float* pack_out = nullptr) {
+  const char* const who = "amh_pooled_update";
+  if (int rc = enter(h, who, false)) return rc;
+  if (!sums || !pooled_ok(in) || !pooled_ok(out)) return fail(h, AMH_EINVAL, "amh_pooled_update: bad arguments");
+  if (k_steps < 1 || h->cfg.num_warmup % k_steps != 0)
+    return fail(h, AMH_EINVAL, "amh_pooled_update: k_steps must be >= 1 and divide num_warmup");
+  if (h->cfg.dim > 64 && !amh::pooled_big_model(h->model_id, h->cfg.dim))
+    return fail(h, AMH_EINVAL, "amh_pooled_update: d > 64 needs d % 32 == 0 in the pooled mode");
+  if (int rc = check_device_flag(h)) return rc;
+  if (int rc = use_device(h, who)) return rc;
+  amh::PooledUpdateParams p{};
+  p.d = h->cfg.dim;
+  p.W = h->cfg.num_warmup;
+  p.a = h->cfg.lr_decay;
+  p.target = h->cfg.target_accept_prob;
+  p.sums = sums;
+  p.in = *in;
+  p.out = *out;
+  p.K = k_steps;
+  hipError_t e;
+  if (amh::pooled_big_model(h->model_id, p.d)) {
+    if (int rc = reserve_update_scratch(h, stream, who)) return rc;
+    p.scratch = h->upd.as<float>();
+    if (p.d == 64 && h->err_host == nullptr) {
+      e = hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped);
+      if (e == hipSuccess) {
+        *h->err_host = 0;
+        e = hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0);
+      }
+      if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update/hipHostMalloc");
+    }
+    p.err_flag = h->err_dev;
+    p.pack_out = (p.d > 64) ? pack_out : nullptr;
+    if (h->noise.ptr && h->noise_C > 0 && h->noise_C <= h->noise_cap && in->rng_key == h->noise_keys &&
+        !diag_env_off("AMH_POOLED_NOISE_AHEAD")) {  // =0 draws no noise ahead (each stats kernel draws its own)
+      p.noise_C = h->noise_C;  // the chains (and keys) of the stats call this update follows
+      p.keys = (const uint32_t*)in->rng_key;
+      p.xrec = h->noise.as<uint4>();
+      p.xi = amh::noise_xi(h->noise.as<float>(), h->noise_cap);
+    }
+    if (deferred && deferred->partials) {
+      p.red_partials = deferred->partials;
+      p.red_chunks = deferred->n_chunks;
+      p.red_accumulate = deferred->accumulate;
+      p.red_blocks = amh::pooled_reduce64_blocks(amh::pooled_big_tile_V(p.d));
+      p.sums_out = const_cast<double*>(sums);
+    }
+    e = amh::run_pooled_big_update(p, (hipStream_t)stream, sigma_ready);
+  } else {
+    e = amh::run_pooled_update(p, (hipStream_t)stream);
+  }
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update");
+  return AMH_OK;
 }
 
 // The pooled transition around the caller's potential.  Nothing is kept in
 // the handle between the two calls: with the shared L the proposal is a
 // product over chains (no per-chain solves), and the accept pass reads the
 // proposals and regenerates u from (key, i + t).
-static int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
-                             const char* who, amh::PooledExtParams* p) {
-  if (!h) return fail(nullptr, AMH_EINVAL, std::string(who) + ": null handle");
+int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, const char* who,
+                      amh::PooledExtParams* p) {
+  if (int rc = enter(h, who, false)) return rc;
   if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, std::string(who) + ": needs AMH_MODEL_EXTERNAL");
   const int d = h->cfg.dim;
   if (d > 64 && !amh::pooled_big_model(h->model_id, d))
@@ -1002,109 +1023,45 @@ static int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled
   return AMH_OK;
 }
 
-int amh_pooled_propose(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, float* zprop,
-                       void* stream) {
-  amh::PooledExtParams p;
-  if (int rc = pooled_ext_params(h, num_chains, in, t, "amh_pooled_propose", &p)) return rc;
-  if (!zprop) return fail(h, AMH_EINVAL, "amh_pooled_propose: bad arguments");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_propose/hipSetDevice");
-  p.zprop = zprop;
-  e = amh::run_pooled_ext_propose(p, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_propose");
-  return AMH_OK;
-}
-
-int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
-                              const float* zprop, const float* pe_prop, float* z_out, float* pe_out, double* sums,
-                              int32_t accumulate, void* stream) {
-  amh::PooledExtParams p;
-  if (int rc = pooled_ext_params(h, num_chains, in, t, "amh_pooled_stats_external", &p)) return rc;
-  if (!zprop || !pe_prop || !z_out || !pe_out || !sums)
-    return fail(h, AMH_EINVAL, "amh_pooled_stats_external: bad arguments");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external/hipSetDevice");
-  const bool big = amh::pooled_big_model(h->model_id, p.d);
-  const int64_t vrow = big ? amh::pooled_big_tile_V(p.d) : p.d + (int64_t)p.d * (p.d + 1) / 2 + 2;
-  if (int rc = grow_partials(h, amh::pooled_ext_chunks(num_chains, p.d), vrow, stream,
-                             "amh_pooled_stats_external/hipMalloc"))
-    return rc;
-  p.zprop = const_cast<float*>(zprop);
-  p.pe_prop = pe_prop;
-  p.z_out = z_out;
-  p.pe_out = pe_out;
-  p.partials = h->partials;
-  e = amh::run_pooled_ext_stats(p, sums, accumulate != 0, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external");
-  return AMH_OK;
-}
-
-}  // extern "C"
-
-static int pooled_update_impl(amh_handle* h, const double* sums, const amh_pooled_state* in,
-                              const amh_pooled_state* out, int32_t k_steps, void* stream, bool sigma_ready,
-                              const DeferredReduce* deferred, float* pack_out) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_pooled_update: null handle");
-  if (!sums || !pooled_ok(in) || !pooled_ok(out)) return fail(h, AMH_EINVAL, "amh_pooled_update: bad arguments");
-  if (k_steps < 1 || h->cfg.num_warmup % k_steps != 0)
-    return fail(h, AMH_EINVAL, "amh_pooled_update: k_steps must be >= 1 and divide num_warmup");
-  if (h->cfg.dim > 64 && !amh::pooled_big_model(h->model_id, h->cfg.dim))
-    return fail(h, AMH_EINVAL, "amh_pooled_update: d > 64 needs d % 32 == 0 in the pooled mode");
-  if (int rc = check_device_flag(h)) return rc;
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update/hipSetDevice");
-  amh::PooledUpdateParams p{};
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.sums = sums;
-  p.in = *in;
-  p.out = *out;
-  p.K = k_steps;
-  if (amh::pooled_big_model(h->model_id, p.d)) {
-    const size_t need = ((size_t)p.d * (p.d + 4) / 2 + 8 + (size_t)p.d) * sizeof(float);
-    const bool fresh = need > h->upd_bytes;
-    int rc = grow(h, &h->upd_buf, &h->upd_bytes, need, stream, "amh_pooled_update/hipMalloc");
-    if (rc != AMH_OK) return rc;
-    if (fresh) {  // the post kernel's arrival ticket starts at zero (its last block resets it)
-      e = hipMemsetAsync(h->upd_buf, 0, h->upd_bytes, (hipStream_t)stream);
-      if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update/hipMemsetAsync");
-    }
-    p.scratch = h->upd_buf;
-    if (p.d == 64 && h->err_host == nullptr) {
-      e = hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped);
-      if (e == hipSuccess) {
-        *h->err_host = 0;
-        e = hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0);
-      }
-      if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update/hipHostMalloc");
-    }
-    p.err_flag = h->err_dev;
-    p.pack_out = (p.d > 64) ? pack_out : nullptr;
-    if (h->noise_buf && h->noise_C > 0 && h->noise_C <= h->noise_cap && in->rng_key == h->noise_keys &&
-        !noise_ahead_off()) {
-      p.noise_C = h->noise_C;  // the chains (and keys) of the stats call this update follows
-      p.keys = (const uint32_t*)in->rng_key;
-      p.xrec = (uint4*)h->noise_buf;
-      p.xi = h->noise_buf + 4 * h->noise_cap;
-    }
-    if (deferred && deferred->partials) {
-      p.red_partials = deferred->partials;
-      p.red_chunks = deferred->n_chunks;
-      p.red_accumulate = deferred->accumulate;
-      p.red_blocks = amh::pooled_reduce64_blocks(amh::pooled_big_tile_V(p.d));
-      p.sums_out = const_cast<double*>(sums);
-    }
-    e = amh::run_pooled_big_update(p, (hipStream_t)stream, sigma_ready);
-  } else {
-    e = amh::run_pooled_update(p, (hipStream_t)stream);
+// ncclAllReduce / ncclGetErrorString of the RCCL instance already in the
+// process (the caller created `comm` with it: torch's librccl.so.1, found by
+// soname without loading anything), else the system librccl.so.1
+typedef int (*nccl_allreduce_fn)(const void*, void*, size_t, int, int, void*, void*);
+typedef const char* (*nccl_errstr_fn)(int);
+void* rccl_handle() {
+  static void* hd = nullptr;
+  if (hd == nullptr) {
+    hd = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
+    if (hd == nullptr) hd = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);
+    if (hd == nullptr) hd = dlopen("librccl.so.1", RTLD_NOW);
   }
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_update");
-  return AMH_OK;
+  return hd;
 }
+
+}  // namespace
 
 extern "C" {
+
+int amh_pooled_sums_size(int32_t dim, int64_t* v) {
+  if (dim < 1 || dim > 256 || !v) return fail(nullptr, AMH_EINVAL, "amh_pooled_sums_size: bad arguments");
+  *v = amh::pooled_sums_len(dim);
+  return AMH_OK;
+}
+
+int amh_pooled_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
+                       float* z_out, float* pe_out, double* sums, void* stream) {
+  return pooled_stats_impl(h, num_chains, in, k_steps, z_out, pe_out, sums, stream, false, nullptr);
+}
+
+int amh_pooled_stats(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, float* z_out, float* pe_out,
+                     double* sums, void* stream) {
+  return amh_pooled_stats_k(h, num_chains, in, 1, z_out, pe_out, sums, stream);
+}
+
+int amh_pooled_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in, const amh_pooled_state* out,
+                        int32_t k_steps, void* stream) {
+  return pooled_update_impl(h, sums, in, out, k_steps, stream, false);
+}
 
 int amh_pooled_update(amh_handle* h, const double* sums, const amh_pooled_state* in, const amh_pooled_state* out,
                       void* stream) {
@@ -1113,10 +1070,12 @@ int amh_pooled_update(amh_handle* h, const double* sums, const amh_pooled_state*
 
 int amh_pooled_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, const amh_pooled_state* out,
                       int32_t n_steps, int32_t sync_every, double* sums, void* stream) {
+  if (int rc = enter(h, "amh_pooled_step", false)) return rc;
   if (n_steps < 0 || sync_every < 1 || n_steps % sync_every != 0)
     return fail(h, AMH_EINVAL, "amh_pooled_step: n_steps must be a non-negative multiple of sync_every");
+  if (!pooled_ok(in) || !pooled_ok(out) || !sums) return fail(h, AMH_EINVAL, "amh_pooled_step: bad arguments");
   const amh_pooled_state* src = in;
-  const bool big = h && h->model_id && amh::pooled_big_model(h->model_id, h->cfg.dim) && h->cfg.dim > 64;
+  const bool big = h->model_id && amh::pooled_big_model(h->model_id, h->cfg.dim) && h->cfg.dim > 64;
   for (int32_t t = 0; t < n_steps; t += sync_every) {
     bool ready = false;  // one rank, no exchange: the reduction also forms Sigma'
     DeferredReduce dr;   // (d = 64: or is left to the update launch)
@@ -1126,7 +1085,7 @@ int amh_pooled_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_state*
                                &ready, &dr, t > 0);
     if (rc != AMH_OK) return rc;
     rc = pooled_update_impl(h, sums, src, out, sync_every, stream, ready, &dr,
-                            (big && t + sync_every < n_steps) ? h->split_buf : nullptr);
+                            (big && t + sync_every < n_steps) ? h->split.as<float>() : nullptr);
     if (rc != AMH_OK) return rc;
     src = out;
   }
@@ -1138,23 +1097,42 @@ int amh_pooled_step(amh_handle* h, int64_t num_chains, const amh_pooled_state* i
   return amh_pooled_step_k(h, num_chains, in, out, n_steps, 1, sums, stream);
 }
 
-// ncclAllReduce / ncclGetErrorString of the RCCL instance already in the
-// process (the caller created `comm` with it: torch's librccl.so.1, found by
-// soname without loading anything), else the system librccl.so.1
-typedef int (*nccl_allreduce_fn)(const void*, void*, size_t, int, int, void*, void*);
-typedef const char* (*nccl_errstr_fn)(int);
-static void* rccl_handle() {
-  static void* hd = nullptr;
-  if (hd == nullptr) {
-    hd = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-    if (hd == nullptr) hd = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);
-    if (hd == nullptr) hd = dlopen("librccl.so.1", RTLD_NOW);
-  }
-  return hd;
+int amh_pooled_propose(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, float* zprop,
+                       void* stream) {
+  amh::PooledExtParams p;
+  if (int rc = pooled_ext_params(h, num_chains, in, t, "amh_pooled_propose", &p)) return rc;
+  if (!zprop) return fail(h, AMH_EINVAL, "amh_pooled_propose: bad arguments");
+  if (int rc = use_device(h, "amh_pooled_propose")) return rc;
+  p.zprop = zprop;
+  const hipError_t e = amh::run_pooled_ext_propose(p, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_propose");
+  return AMH_OK;
+}
+
+int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t,
+                              const float* zprop, const float* pe_prop, float* z_out, float* pe_out, double* sums,
+                              int32_t accumulate, void* stream) {
+  const char* const who = "amh_pooled_stats_external";
+  amh::PooledExtParams p;
+  if (int rc = pooled_ext_params(h, num_chains, in, t, who, &p)) return rc;
+  if (!zprop || !pe_prop || !z_out || !pe_out || !sums)
+    return fail(h, AMH_EINVAL, "amh_pooled_stats_external: bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  if (int rc = reserve_partials(h, amh::pooled_ext_chunks(num_chains, p.d), amh::pooled_big_model(h->model_id, p.d),
+                             stream, who))
+    return rc;
+  p.zprop = const_cast<float*>(zprop);
+  p.pe_prop = pe_prop;
+  p.z_out = z_out;
+  p.pe_out = pe_out;
+  p.partials = h->partials.as<double>();
+  const hipError_t e = amh::run_pooled_ext_stats(p, sums, accumulate != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external");
+  return AMH_OK;
 }
 
 int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm, void* stream) {
-  if (!h) return fail(nullptr, AMH_EINVAL, "amh_pooled_allreduce: null handle");
+  if (int rc = enter(h, "amh_pooled_allreduce", false)) return rc;
   if (!sums || !rccl_comm || n < 0) return fail(h, AMH_EINVAL, "amh_pooled_allreduce: null sums / communicator");
   void* hd = rccl_handle();
   auto ar = hd ? (nccl_allreduce_fn)dlsym(hd, "ncclAllReduce") : nullptr;
@@ -1169,7 +1147,12 @@ int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm
   return AMH_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------- diagnostics --
 #ifdef AMH_STAMPS
+extern "C" {
+
 // diagnostic build only: copy the step kernel's per-wave phase stamps
 int amh_diag_stamps(void* host, int64_t bytes) {
   return amh::diag_stamps_copy(host, (size_t)bytes) == hipSuccess ? 0 : -1;
@@ -1180,5 +1163,6 @@ int amh_diag_upd_stamps(void* host) { return amh::diag_upd_stamps_copy(host) == 
 int amh_diag_f64_stamps(void* host) { return amh::diag_f64_stamps_copy(host) == hipSuccess ? 0 : -1; }
 // pooled d = 64 update launch timeline (16 x u64, 100 MHz clock; copied, then cleared)
 int amh_diag_u64_timeline(void* host) { return amh::diag_u64_timeline_copy(host) == hipSuccess ? 0 : -1; }
-#endif
+
 }  // extern "C"
+#endif

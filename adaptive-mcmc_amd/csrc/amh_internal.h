@@ -19,6 +19,14 @@ namespace amh {
 // fall back to the device routine.
 constexpr int32_t kGammaTab = 1 << 20;
 
+// compute units of the current device (persistent grids are sized by it)
+inline int cu_count() {
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus;
+}
+
 struct ModelArgs {
   const float* data;  // device, model-specific layout (include/amh.h)
   int64_t n;          // N rows (regression models)
@@ -89,6 +97,17 @@ struct AsssPnxParams {
 // pooled covariance (amh_pooled.hip)
 constexpr int kPoolWaves = 16;  // waves (of one chain each) per chunk block
 
+// the pooled sums [S_d (d) | S_dd packed (d(d+1)/2) | S_a | N] (amh_pooled_sums_size)
+constexpr int64_t pooled_sums_len(int d) { return d + (int64_t)d * (d + 1) / 2 + 2; }
+// the d >= 64 update's staging: the factor in the 4-row-aligned layout, then
+// ok, gamma, e^lam, e^lam', 4 spare, d column sums (PooledUpdateParams::scratch)
+constexpr size_t pooled_factor_floats(int d) { return (size_t)d * (d + 4) / 2; }
+constexpr size_t pooled_update_scratch_floats(int d) { return pooled_factor_floats(d) + 8 + (size_t)d; }
+// d >= 64 noise drawn ahead: `cap` records (i, key0, key1, u bits), then xi [cap][d]
+constexpr size_t kNoiseRecordBytes = sizeof(uint4);
+constexpr size_t noise_row_bytes(int d) { return kNoiseRecordBytes + (size_t)d * sizeof(float); }
+inline float* noise_xi(float* buf, int64_t cap) { return buf + (kNoiseRecordBytes / sizeof(float)) * cap; }
+
 // chains each wave of a chunk takes (bit spec: fixes the summation order)
 __host__ __device__ inline int pooled_cpw(int64_t C) {
   const int64_t c = (C + 4095) / 4096;
@@ -149,7 +168,7 @@ struct PooledUpdateParams {
   float a, target;
   const double* sums;
   amh_pooled_state in, out;
-  float* scratch;  // d >= 64: d(d+4)/2 floats (4-row-aligned factor), ok, gamma, e^lam, e^lam', 4 spare, d column sums
+  float* scratch;  // d >= 64: pooled_update_scratch_floats(d)
   int32_t K;       // transitions per pooled update (the sums cover K * C chain-steps)
   // d > 64: the next step's noise for chains [0, noise_C) is drawn by the
   // update launch's extra blocks into xi / xrec (PooledStatsParams)
@@ -178,10 +197,11 @@ int pooled_reduce64_blocks(int64_t V);  // reduce blocks of the d = 64 partial r
 hipError_t run_pooled_stats(int model_id, const PooledStatsParams& p, double* sums, hipStream_t s);
 // large dimensions (amh_big_pooled.hip): chunks of 256 chains
 int64_t pooled_big_chunks(int64_t C, int d);
-int64_t pooled_big_pack_floats(int d);
-int64_t pooled_big_tile_V(int d);  // partial row length of the fused large-d stats (d > 64)  // scratch floats of the fused large-d stats (A-operand tiles)
+int64_t pooled_big_pack_floats(int d);  // scratch floats of the fused large-d stats (A-operand tiles)
+int64_t pooled_big_tile_V(int d);       // partial row length of the fused large-d stats (d > 64)
 int64_t pooled_scratch_rows(int64_t n_chunks);  // partials + group sums of pooled_reduce
-hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* xprop, float* pep, double* sums, hipStream_t s);
+// pack: pooled_big_pack_floats(d) floats of scratch (d > 64; unused at d = 64)
+hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* pack, double* sums, hipStream_t s);
 hipError_t run_pooled_big_update(const PooledUpdateParams& p, hipStream_t s, bool sigma_ready = false);
 // chunk partials -> this rank's sums (accumulate: sums += them), d < 64:
 // double rows, group sums after the partials (pooled_scratch_rows); d >= 64:

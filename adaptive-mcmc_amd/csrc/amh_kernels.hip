@@ -1577,9 +1577,7 @@ hipError_t launch_step64(const StepParams& p, hipStream_t s) {
   int per_cu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, WPB * 64, shm);
   if (e != hipSuccess) return e;
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   if (per_cu < 1) per_cu = 1;
   const int64_t need = (p.C + WPB - 1) / WPB;
   int64_t blocks = (int64_t)cus * per_cu;
@@ -1611,9 +1609,7 @@ hipError_t launch_step(const StepParams& p, hipStream_t s) {
   int per_cu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlockStep, shm);
   if (e != hipSuccess) return e;
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   if (per_cu < 1) per_cu = 1;
   const int64_t need = (n_items + WPB - 1) / WPB;
   int64_t blocks = (int64_t)cus * per_cu;

@@ -336,7 +336,7 @@ hipError_t launch_pooled_stats(const PooledStatsParams& p, double* sums, hipStre
   const int cpw = pooled_cpw(p.C);
   const int64_t chunk = (int64_t)kPoolWaves * cpw;
   const int64_t n_chunks = (p.C + chunk - 1) / chunk;
-  const int64_t V = d + (int64_t)d * (d + 1) / 2 + 2;
+  const int64_t V = pooled_sums_len(d);
   hipLaunchKernelGGL((pooled_stats_kernel<M, EXACT>), dim3((unsigned)n_chunks), dim3(kPoolWaves * 64), shm, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_ext_propose_kernel(Poo
 __global__ __launch_bounds__(kPoolWaves * 64) void pooled_ext_stats_kernel(PooledExtParams p) {
   extern __shared__ float tree[];
   const int d = p.d;
-  const int64_t V = d + (int64_t)d * (d + 1) / 2 + 2;
+  const int64_t V = pooled_sums_len(d);
   const int r = lane_id();
   const bool act = r < d;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
@@ -359,9 +359,7 @@ __global__ __launch_bounds__(64 * kStatWaves) void pooled_ext_stats_big_kernel(P
 namespace {
 bool ext_big(int d) { return d >= 64 && d <= 256 && d % 32 == 0; }
 int device_cus() {
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   return cus > 0 ? cus : 1;
 }
 }  // namespace
@@ -405,7 +403,7 @@ hipError_t run_pooled_ext_stats(const PooledExtParams& p, double* sums, int accu
   if (d < 1 || (d > 64 && !ext_big(d))) return hipErrorInvalidValue;
   const int64_t n_chunks = pooled_ext_chunks(p.C, d);
   if (!ext_big(d)) {
-    const int64_t V = d + (int64_t)d * (d + 1) / 2 + 2;
+    const int64_t V = pooled_sums_len(d);
     hipLaunchKernelGGL(pooled_ext_stats_kernel, dim3((unsigned)n_chunks), dim3(kPoolWaves * 64),
                        kPooledTreeFloats * sizeof(float), s, p);
     hipError_t e = hipGetLastError();

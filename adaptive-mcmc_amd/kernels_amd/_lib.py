@@ -26,16 +26,6 @@ AMH_MODEL_EXTERNAL = 7  # the caller's potential (amh_propose / amh_step_externa
 AMH_STEP_PROPOSAL_READY = 1
 AMH_STEP_KEEP_PROPOSAL = 2
 
-# every symbol include/amh.h declares
-EXPORTS = ("amh_version", "amh_last_error", "amh_create", "amh_destroy", "amh_bind_model", "amh_init",
-           "amh_step", "amh_step_chained", "amh_potential", "amh_sample_pnx", "amh_chain_keys", "amh_pooled_sums_size",
-           "amh_pooled_stats", "amh_pooled_update", "amh_pooled_step", "amh_pooled_stats_k", "amh_pooled_update_k",
-           "amh_pooled_step_k", "amh_asss_step",
-           "amh_asss_sample_pnx", "amh_kernel_sum_scratch", "amh_kernel_sum", "amh_pairwise_dist2",
-           "amh_normals", "amh_sinkhorn_lse", "amh_check_device", "amh_pooled_allreduce", "amh_propose",
-           "amh_step_external", "amh_pnx_propose", "amh_pnx_accept", "amh_pooled_propose",
-           "amh_pooled_stats_external")
-
 
 class AmhConfig(ctypes.Structure):
     _fields_ = [("dim", ctypes.c_int32), ("num_warmup", ctypes.c_int32), ("lr_decay", ctypes.c_float),
@@ -58,6 +48,57 @@ class AmhPooledState(ctypes.Structure):
                                                "scale", "log_step_size", "as_change", "cov")]
 
 
+def _signatures():
+    P, I, I32, I64, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    KEY = ctypes.POINTER(ctypes.c_uint32)
+    S, COL, PS = ctypes.POINTER(AmhState), ctypes.POINTER(AmhCollect), ctypes.POINTER(AmhPooledState)
+    return {
+        # core
+        "amh_version": (I, []),
+        "amh_last_error": (ctypes.c_char_p, [P]),
+        "amh_create": (I, [ctypes.POINTER(AmhConfig), I, ctypes.POINTER(P)]),
+        "amh_destroy": (I, [P]),
+        "amh_check_device": (I, [P]),
+        "amh_bind_model": (I, [P, I32, P, I64, ctypes.POINTER(I64), I32]),
+        "amh_init": (I, [P, KEY, I64, I64, P, S, P]),
+        "amh_step": (I, [P, I64, S, S, I32, COL, P]),
+        "amh_step_chained": (I, [P, I64, S, S, I32, COL, I32, P]),
+        "amh_potential": (I, [P, P, P, I64, P]),
+        "amh_sample_pnx": (I, [P, KEY, P, I64, I64, P, P, F, I32, P, P]),
+        "amh_chain_keys": (I, [KEY, I64, I64, P, P]),
+        # external potential
+        "amh_propose": (I, [P, I64, S, P, P]),
+        "amh_step_external": (I, [P, I64, S, S, P, P, P, COL, P]),
+        "amh_pnx_propose": (I, [P, KEY, P, I64, P, F, I32, P, P]),
+        "amh_pnx_accept": (I, [P, KEY, P, P, I64, P, P, I32, P]),
+        # ASSS
+        "amh_asss_step": (I, [P, I64, S, S, I32, COL, P]),
+        "amh_asss_sample_pnx": (I, [P, KEY, P, I64, I64, P, P, I32, P, P]),
+        # evaluation
+        "amh_kernel_sum_scratch": (I64, [I64, I64]),
+        "amh_kernel_sum": (I, [P, I64, P, I64, I32, F, I32, P, P, P]),
+        "amh_pairwise_dist2": (I, [P, I64, P, I64, I32, P, P]),
+        "amh_normals": (I, [KEY, I64, P, P]),
+        "amh_sinkhorn_lse": (I, [P, I64, I64, P, F, F, P, P]),
+        # pooled covariance
+        "amh_pooled_sums_size": (I, [I32, ctypes.POINTER(I64)]),
+        "amh_pooled_stats": (I, [P, I64, PS, P, P, P, P]),
+        "amh_pooled_update": (I, [P, P, PS, PS, P]),
+        "amh_pooled_step": (I, [P, I64, PS, PS, I32, P, P]),
+        "amh_pooled_stats_k": (I, [P, I64, PS, I32, P, P, P, P]),
+        "amh_pooled_update_k": (I, [P, P, PS, PS, I32, P]),
+        "amh_pooled_step_k": (I, [P, I64, PS, PS, I32, I32, P, P]),
+        "amh_pooled_allreduce": (I, [P, P, I64, P, P]),
+        "amh_pooled_propose": (I, [P, I64, PS, I32, P, P]),
+        "amh_pooled_stats_external": (I, [P, I64, PS, I32, P, P, P, P, P, I32, P]),
+    }
+
+
+# every symbol include/amh.h declares: name -> (restype, argtypes)
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
+
+
 class AmhError(RuntimeError):
     pass
 
@@ -78,66 +119,10 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise AmhError(f"libamh.so not built ({LIB_PATH}); run `make -C {CSRC}` or __graft_entry__.build()")
     L = ctypes.CDLL(LIB_PATH)
-    P, I32, I64, F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    L.amh_version.restype = ctypes.c_int
-    L.amh_last_error.argtypes = [P]
-    L.amh_last_error.restype = ctypes.c_char_p
-    L.amh_create.argtypes = [ctypes.POINTER(AmhConfig), ctypes.c_int, ctypes.POINTER(P)]
-    L.amh_destroy.argtypes = [P]
-    L.amh_check_device.argtypes = [P]
-    L.amh_check_device.restype = ctypes.c_int
-    L.amh_bind_model.argtypes = [P, I32, P, I64, ctypes.POINTER(I64), I32]
-    L.amh_init.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), I64, I64, P, ctypes.POINTER(AmhState), P]
-    L.amh_step.argtypes = [P, I64, ctypes.POINTER(AmhState), ctypes.POINTER(AmhState), I32,
-                           ctypes.POINTER(AmhCollect), P]
-    L.amh_step_chained.argtypes = [P, I64, ctypes.POINTER(AmhState), ctypes.POINTER(AmhState), I32,
-                                   ctypes.POINTER(AmhCollect), I32, P]
-    L.amh_step_chained.restype = ctypes.c_int
-    L.amh_potential.argtypes = [P, P, P, I64, P]
-    L.amh_sample_pnx.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), P, I64, I64, P, P, F, I32, P, P]
-    L.amh_chain_keys.argtypes = [ctypes.POINTER(ctypes.c_uint32), I64, I64, P, P]
-    L.amh_asss_step.argtypes = [P, I64, ctypes.POINTER(AmhState), ctypes.POINTER(AmhState), I32,
-                                ctypes.POINTER(AmhCollect), P]
-    L.amh_asss_step.restype = ctypes.c_int
-    L.amh_asss_sample_pnx.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), P, I64, I64, P, P, I32, P, P]
-    L.amh_propose.argtypes = [P, I64, ctypes.POINTER(AmhState), P, P]
-    L.amh_propose.restype = ctypes.c_int
-    L.amh_step_external.argtypes = [P, I64, ctypes.POINTER(AmhState), ctypes.POINTER(AmhState), P, P, P,
-                                    ctypes.POINTER(AmhCollect), P]
-    L.amh_step_external.restype = ctypes.c_int
-    L.amh_pnx_propose.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), P, I64, P, F, I32, P, P]
-    L.amh_pnx_propose.restype = ctypes.c_int
-    L.amh_pnx_accept.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), P, P, I64, P, P, I32, P]
-    L.amh_pnx_accept.restype = ctypes.c_int
-    L.amh_asss_sample_pnx.restype = ctypes.c_int
-    L.amh_kernel_sum_scratch.argtypes = [I64, I64]
-    L.amh_kernel_sum_scratch.restype = I64
-    L.amh_kernel_sum.argtypes = [P, I64, P, I64, I32, F, I32, P, P, P]
-    L.amh_kernel_sum.restype = ctypes.c_int
-    L.amh_pairwise_dist2.argtypes = [P, I64, P, I64, I32, P, P]
-    L.amh_pairwise_dist2.restype = ctypes.c_int
-    L.amh_normals.argtypes = [ctypes.POINTER(ctypes.c_uint32), I64, P, P]
-    L.amh_normals.restype = ctypes.c_int
-    L.amh_sinkhorn_lse.argtypes = [P, I64, I64, P, F, F, P, P]
-    L.amh_sinkhorn_lse.restype = ctypes.c_int
-    PS = ctypes.POINTER(AmhPooledState)
-    L.amh_pooled_sums_size.argtypes = [I32, ctypes.POINTER(I64)]
-    L.amh_pooled_stats.argtypes = [P, I64, PS, P, P, P, P]
-    L.amh_pooled_update.argtypes = [P, P, PS, PS, P]
-    L.amh_pooled_step.argtypes = [P, I64, PS, PS, I32, P, P]
-    L.amh_pooled_stats_k.argtypes = [P, I64, PS, I32, P, P, P, P]
-    L.amh_pooled_update_k.argtypes = [P, P, PS, PS, I32, P]
-    L.amh_pooled_allreduce.argtypes = [P, P, I64, P, P]
-    L.amh_pooled_step_k.argtypes = [P, I64, PS, PS, I32, I32, P, P]
-    L.amh_pooled_propose.argtypes = [P, I64, PS, I32, P, P]
-    L.amh_pooled_stats_external.argtypes = [P, I64, PS, I32, P, P, P, P, P, I32, P]
-    for name in ("amh_pooled_sums_size", "amh_pooled_stats", "amh_pooled_update", "amh_pooled_step",
-                 "amh_pooled_stats_k", "amh_pooled_update_k", "amh_pooled_step_k", "amh_pooled_allreduce",
-                 "amh_pooled_propose", "amh_pooled_stats_external"):
-        getattr(L, name).restype = ctypes.c_int
-    L.amh_version.argtypes = []
-    for name in EXPORTS[:10]:
-        getattr(L, name).restype = ctypes.c_int if name != "amh_last_error" else ctypes.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     _lib = L
     return L
 

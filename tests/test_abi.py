@@ -84,6 +84,43 @@ def test_calls_fail_cleanly_without_device(lib):
     assert b"amh_pooled_allreduce" in L.amh_last_error(None)
 
 
+def handle_entries():
+    """Every prototype in include/amh.h whose first parameter is the handle,
+    except the two for which a null handle is a valid argument."""
+    src = open(os.path.join(ROOT, "include", "amh.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    names = re.findall(r"^\s*(?:int64_t|int)\s*(amh_\w+)\s*\(\s*amh_handle\s*\*", src, flags=re.M)
+    return sorted(set(names) - {"amh_destroy"})
+
+
+def _zero(ctype):
+    """The zero / null value of a bound argument type."""
+    return None if issubclass(ctype, (ctypes.c_void_p, ctypes._Pointer)) else ctype(0)
+
+
+@pytest.mark.parametrize("name", handle_entries())
+def test_null_handle_is_refused(name, lib):
+    """A null handle with zero / null for everything else is AMH_EINVAL with a
+    message, from every entry that takes a handle: no argument is touched
+    before the handle is checked."""
+    assert len(handle_entries()) >= 20
+    fn = getattr(lib.lib(), name)
+    assert fn.argtypes[0] is ctypes.c_void_p
+    assert fn(*[_zero(t) for t in fn.argtypes]) == -1, name
+    assert lib.lib().amh_last_error(None), name
+
+
+@pytest.mark.parametrize("name", ["amh_pooled_step", "amh_pooled_step_k"])
+def test_pooled_step_refuses_null_handle_with_no_steps(name, lib):
+    """n_steps = 0 is a valid (empty) call, but not on a null handle."""
+    L = lib.lib()
+    st = lib.AmhPooledState()
+    sums = (ctypes.c_double * 8)()
+    sync = () if name == "amh_pooled_step" else (1,)
+    assert getattr(L, name)(None, 1, ctypes.byref(st), ctypes.byref(st), 0, *sync, sums, None) == -1
+    assert b"null handle" in L.amh_last_error(None)
+
+
 def test_product_refuses_cpu_tensors(lib):
     import torch
     with pytest.raises(lib.AmhError):

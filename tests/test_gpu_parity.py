@@ -339,3 +339,57 @@ def test_big_dim_chained_proposal_invalidation(kind, d, C, gpu, orc):
     orc.step(om, ost0, 2, num_warmup=2)
     torch.cuda.synchronize()
     assert_state_bitequal(si, ost0, "inference mode")
+
+
+def _chained_call(k, sin, sout, flags):
+    """amh_step_chained itself, one transition: none of ARWMH._launch's
+    bookkeeping (weak references, version counters) stands in front of it."""
+    from kernels_amd import _lib
+    dev = sin.z.device.index
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().amh_step_chained(k._handle.h, sin.z.shape[0], k._c_state(sin), k._c_state(sout), 1, None,
+                                               flags, _lib.stream_ptr(dev)), k._handle.h)
+    torch.cuda.synchronize()
+    return sout
+
+
+def _head(st, n):
+    """The first n chains of a product state, as views of the same buffers."""
+    return type(st)(*[type(x)(*[y[:n] for y in x]) if isinstance(x, tuple) else x[:n] for x in st])
+
+
+@pytest.mark.parametrize("kind,d,C", [("gaussian", 96, 65), ("diamonds", None, 66)])
+def test_library_ready_guard(kind, d, C, gpu, orc):
+    """The library's own guard on AMH_STEP_PROPOSAL_READY: it honours the flag
+    only for the very buffers, and the chain count, of the call that kept the
+    proposal.  With the flag set on other buffers, or on fewer chains, the
+    propose pass runs all the same and the step stays bit-identical to the
+    oracle; a call that does continue the previous one is exact as well."""
+    from kernels_amd import _lib
+    both = _lib.AMH_STEP_PROPOSAL_READY | _lib.AMH_STEP_KEEP_PROPOSAL
+    k, st, om, ost = _init(kind, C, gpu, orc, d=d, num_warmup=2)
+    for t in range(3):
+        st = k.sample(st, (), {})  # each keeps its next proposal in the handle
+    orc.step(om, ost, 3, num_warmup=2)
+    # same values, another z buffer
+    other = st._replace(z=st.z.clone())
+    s1 = _chained_call(k, other, k._alloc_state(C, om.d, other.z.device), both)
+    orc.step(om, ost, 1, num_warmup=2)
+    assert_state_bitequal(s1, ost, "READY on a cloned z")
+    # another z buffer with other values: the kept proposal would be stale
+    moved = s1._replace(z=s1.z.clone())
+    moved.z[:, 0] += 0.25
+    ost.z[:, 0] += np.float32(0.25)
+    s2 = _chained_call(k, moved, k._alloc_state(C, om.d, moved.z.device), both)
+    orc.step(om, ost, 1, num_warmup=2)
+    assert_state_bitequal(s2, ost, "READY on a cloned and edited z")
+    # the kept buffers, one chain fewer than the proposal was kept for
+    n = C - 1
+    osub = orc.State(*[np.ascontiguousarray(getattr(ost, f)[:n]) for f in ost.__dataclass_fields__])
+    s3 = _chained_call(k, _head(s2, n), k._alloc_state(n, om.d, s2.z.device), both)
+    orc.step(om, osub, 1, num_warmup=2)
+    assert_state_bitequal(s3, osub, "READY with one chain fewer")
+    # legitimately chained: the unchanged output of the previous call
+    s4 = _chained_call(k, s3, k._alloc_state(n, om.d, s3.z.device), both)
+    orc.step(om, osub, 1, num_warmup=2)
+    assert_state_bitequal(s4, osub, "chained call")
