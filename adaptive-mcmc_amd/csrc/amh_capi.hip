@@ -61,6 +61,9 @@ struct amh_handle {
   const uint32_t* noise_keys = nullptr;
   int* err_host = nullptr;     // pooled d = 64: host-mapped device error flag (PooledUpdateParams::err_flag)
   int* err_dev = nullptr;      // ... its device address
+  const float* s64_scale = nullptr;  // d = 64 step kernel: the factor buffer its last launch wrote,
+  int64_t s64_C = 0;                 // that launch's chain count
+  int32_t s64_order = -1;            // and chain order (0 ascending, 1 descending; -1: no launch yet)
   std::string err;
 };
 
@@ -214,6 +217,24 @@ amh::StepParams step_params(const amh_handle* h, int64_t C, const amh_state& in,
   return p;
 }
 
+// The d = 64 Gaussian step kernel (arwmh_step64_kernel, ARWMH and ASSS) walks
+// each block's chain range in either order with the same results.  A launch
+// whose input is what the handle's last such launch wrote (the same factor
+// buffer and chain count) takes the opposite order: its first reads are that
+// launch's last writes, which the memory-side cache still holds (DESIGN.md
+// 3.1).  Any other launch runs ascending.
+bool step64_shape(const amh_handle* h) { return h->model_id == AMH_MODEL_GAUSSIAN && h->cfg.dim == 64; }
+
+int32_t step64_order(const amh_handle* h, const amh::StepParams& p) {
+  return (h->s64_order >= 0 && p.in.scale == h->s64_scale && p.C == h->s64_C) ? 1 - h->s64_order : 0;
+}
+
+void step64_launched(amh_handle* h, const amh::StepParams& p) {
+  h->s64_scale = p.out.scale;
+  h->s64_C = p.C;
+  h->s64_order = p.descending;
+}
+
 // the scratch pointers (xprop, wa, wr, dg, pep) are the caller's to set
 amh::BigParams big_params(const amh_handle* h, int64_t C, const amh_state& in, const amh_state& out,
                           const amh_collect* collect) {
@@ -319,6 +340,13 @@ int amh_create(const amh_config* cfg, int device, amh_handle** out) {
 int amh_check_device(amh_handle* h) {
   if (int rc = enter(h, "amh_check_device", false)) return rc;
   return check_device_flag(h);
+}
+
+int amh_step_order(amh_handle* h, int32_t* order) {
+  if (int rc = enter(h, "amh_step_order", false)) return rc;
+  if (!order) return fail(h, AMH_EINVAL, "amh_step_order: null argument");
+  *order = h->s64_order;
+  return AMH_OK;
 }
 
 int amh_destroy(amh_handle* h) {
@@ -439,7 +467,7 @@ int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, con
   }
   if (collect && collect->thinning < 1) return fail(h, AMH_EINVAL, "amh_step: thinning must be >= 1");
   if (int rc = use_device(h, "amh_step")) return rc;
-  const amh::StepParams p = step_params(h, num_chains, *in, *out, n_steps, collect);
+  amh::StepParams p = step_params(h, num_chains, *in, *out, n_steps, collect);
   const int64_t C = num_chains;
   const hipStream_t s = (hipStream_t)stream;
   if (amh::big_model(h->model_id, p.d)) {
@@ -489,8 +517,10 @@ int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, con
                          return e;
                        });
   }
+  if (step64_shape(h)) p.descending = step64_order(h, p);
   const hipError_t e = amh::run_step(h->model_id, p, s);
   if (e != hipSuccess) return hip_fail(h, e, "amh_step");
+  if (step64_shape(h)) step64_launched(h, p);
   return AMH_OK;
 }
 
@@ -722,8 +752,10 @@ int amh_asss_step(amh_handle* h, int64_t num_chains, const amh_state* in, const 
     }
     return AMH_OK;
   }
+  if (step64_shape(h)) p.descending = step64_order(h, p);
   const hipError_t e = amh::run_asss_step(h->model_id, p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "amh_asss_step");
+  if (step64_shape(h)) step64_launched(h, p);
   return AMH_OK;
 }
 

@@ -50,6 +50,8 @@ struct StepParams {
   const float* ext_z;      // split path: the proposals z' [C][d] that U(z') was evaluated at
   float* xprop_next;       // split path: the NEXT transition's proposal [C][d] (or null), formed as
                            // the propose pass would form it from the stored state
+  int32_t descending;      // d = 64 step kernel: every block walks its chain range from the top (launch-
+                           // uniform; the results do not depend on it, amh_capi.hip step64_order)
 };
 
 struct InitParams {

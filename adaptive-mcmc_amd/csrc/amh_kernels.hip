@@ -39,7 +39,7 @@ __host__ __device__ __forceinline__ int wbuf_floats(int cpw, int d) {
 
 // Issue the DMA of one work item's chain state (global -> this wave's LDS
 // buffer).  Out-of-range bytes (past C) read as zero.
-template <int G, bool EXT>
+template <int G, bool EXT, int AUX = kLoadAux>  // AUX: cache policy of the factor's DMA loads
 __device__ __forceinline__ void prefetch_item(const StepParams& p, int64_t first, int d, float* wb, int lane) {
   constexpr int CPW = Geo<G>::CPW;
   const uint32_t P = (uint32_t)(d * (d + 1) / 2);
@@ -57,10 +57,10 @@ __device__ __forceinline__ void prefetch_item(const StepParams& p, int64_t first
     // DMA inside this wave's buffer (an LDS-DMA writes base + 4*size*lane)
     const uint32_t n16 = vec ? (total / 1024u) * 1024u : 0u;
     for (uint32_t o = 0; o < n16; o += 1024u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 16, (int)(o + 16u * lane), 0, 0, kLoadAux);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 16, (int)(o + 16u * lane), 0, 0, AUX);
     for (uint32_t o = n16; o < total; o += 256u) {
       if (o + 4u * lane < total)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 4, (int)(o + 4u * lane), 0, 0, kLoadAux);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 4, (int)(o + 4u * lane), 0, 0, AUX);
     }
   }
   {
@@ -835,6 +835,13 @@ __global__ void chain_keys_kernel(uint32_t key0, uint32_t key1, int64_t offset, 
 //   ds_read_b128, in place of v_readlane + s_nop per column.  Only sweep 1,
 //   whose w_j is serial, still uses v_readlane.
 constexpr int kS64Waves = 16;
+// Cache policy of this kernel's factor traffic (its own: kLoadAux / kStoreAux
+// serve the other kernels).  The flush's stores are plain so that the next,
+// oppositely ordered launch finds what this one wrote last in the memory-side
+// cache; the DMA loads stay nt (read once per launch).  The other three pairs
+// lost on the kernel, though not on the probe (tools/ic_reuse.hip).
+constexpr int kS64LoadAux = 2;
+constexpr int kS64StoreAux = 0;
 constexpr int kS64EB = 8;  // proposal: broadcast columns per LDS wait
 constexpr int kS64PB = 8;  // potential: columns per LDS wait
 static_assert(kS64EB == 8 && kS64PB == 8, "the batch readers (lds_ld4x2w / lds_ld4x4w) read two quarter-vectors per stream");
@@ -1199,7 +1206,17 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   extern __shared__ float lds[];
   M::stage(lds, p.model, D);
   float* tick = lds + kS64Model + WPB * kS64WB;
-  if (threadIdx.x == 0) tick[0] = 0.0f;
+  // The block's ticket counter hands out the block-local chain index: 0, 1,
+  // 2, ... in an ascending launch, n - 1, n - 2, ..., 0 in a descending one
+  // (n = the block's chain count), so that what one launch wrote last is what
+  // the next one reads first and the memory-side cache still holds it
+  // (DESIGN.md 3.1).  Chains are independent: the order changes no bit.  Past
+  // the last chain the counter reads n, n + 1, ... or wraps to 2^32 - 1,
+  // 2^32 - 2, ...: either way an index >= n, "no item".
+  const uint32_t tk_step = p.descending ? ~0u : 1u;
+  const int64_t blk_lo = p.C * (int64_t)blockIdx.x / gridDim.x;  // one chain per wave
+  const int64_t blk_hi = p.C * ((int64_t)blockIdx.x + 1) / gridDim.x;
+  if (threadIdx.x == 0) tick[0] = __uint_as_float(p.descending ? (uint32_t)(blk_hi - blk_lo) - 1u : 0u);
   __syncthreads();
   const auto mctx = M::prepare(p.model, D, lane_id());
 #ifdef AMH_STAMPS
@@ -1210,7 +1227,6 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 #endif
 
   const int64_t C = p.C;
-  const int64_t n_items = C;  // one chain per wave
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
   float* wb = lds + kS64Model + wave_in_block * kS64WB;
   const uint32_t wb_a = lds_addr(wb);
@@ -1227,14 +1243,12 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   int64_t prev = -1;
   bool prev_upd = false;
 
-  const int64_t blk_lo = n_items * (int64_t)blockIdx.x / gridDim.x;
-  const int64_t blk_hi = n_items * ((int64_t)blockIdx.x + 1) / gridDim.x;
   const int64_t kEnd = blk_hi;  // "no item" sentinel
   const uint32_t tk_addr = lds_addr(tick);
   auto ticket = [&]() -> int64_t {
     uint32_t v = 0;
     if (lane_id() == 0) {
-      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(tk_addr), "v"(1u) : "memory");
+      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(tk_addr), "v"(tk_step) : "memory");
     }
     return blk_lo + (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v);
   };
@@ -1287,14 +1301,14 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       static_for<3>([&](auto Q) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint32x4_t_, v[(int)Q]), Lout.rs,
                                                (int)(1024u * (3 * G + Q) + 16u * (uint32_t)lane_id()), 0,
-                                               kStoreAux);
+                                               kS64StoreAux);
       });
     });
   };
 
   int64_t item = ticket();
   int64_t nxt = item < kEnd ? ticket() : kEnd;
-  if (item < kEnd) prefetch_item<64, false>(p, item, D, wb, lane_id());
+  if (item < kEnd) prefetch_item<64, false, kS64LoadAux>(p, item, D, wb, lane_id());
   for (; item < kEnd;) {
     int lane = lane_id();
     asm volatile("" : "+v"(lane));
@@ -1364,7 +1378,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     s64_wait();  // every LDS read of the buffer is done before the DMA refills it
     int64_t nxt2 = kEnd;
     if (nxt < kEnd) {
-      prefetch_item<64, false>(p, nxt, D, wb, lane);
+      prefetch_item<64, false, kS64LoadAux>(p, nxt, D, wb, lane);
       nxt2 = ticket();
     }
     __builtin_amdgcn_s_setprio(0);

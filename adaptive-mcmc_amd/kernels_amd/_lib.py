@@ -59,6 +59,7 @@ def _signatures():
         "amh_create": (I, [ctypes.POINTER(AmhConfig), I, ctypes.POINTER(P)]),
         "amh_destroy": (I, [P]),
         "amh_check_device": (I, [P]),
+        "amh_step_order": (I, [P, ctypes.POINTER(I32)]),
         "amh_bind_model": (I, [P, I32, P, I64, ctypes.POINTER(I64), I32]),
         "amh_init": (I, [P, KEY, I64, I64, P, S, P]),
         "amh_step": (I, [P, I64, S, S, I32, COL, P]),
@@ -175,6 +176,12 @@ class Handle:
             torch.cuda.current_stream(data.device).synchronize()
             check(self._lib.amh_bind_model(self.h, model_id, ptr(data), data.numel(), ip, len(iparams)), self.h)
         self._data = data  # keep alive
+
+    def step_order(self) -> int:
+        """Chain order of the last d = 64 step launch: 0 ascending, 1 descending, -1 none yet."""
+        order = ctypes.c_int32(-2)
+        check(self._lib.amh_step_order(self.h, ctypes.byref(order)), self.h)
+        return order.value
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

@@ -125,6 +125,16 @@ int amh_destroy(amh_handle* h);
  * whose guards (arwmh.py:171, :191) cannot fail this way. */
 int amh_check_device(amh_handle* h);
 
+/* The chain order of the handle's last d = 64 Gaussian step launch (amh_step,
+ * amh_step_chained, amh_asss_step): *order = 0 when every block walked its
+ * chains ascending, 1 when descending, -1 when the handle has launched none
+ * yet.  A launch whose input factor buffer (in->scale) and chain count are
+ * those the previous such launch wrote runs in the opposite order, so that it
+ * first reads what that launch wrote last (still held by the memory-side
+ * cache); any other launch runs ascending.  The order changes no result; this
+ * entry only makes the choice observable.  No counterpart in the reference. */
+int amh_step_order(amh_handle* h, int32_t* order);
+
 /* Model plug-in (arwmh.py:109-116 / the scripts' numpyro models).
  * data: device pointer, n_data floats; iparams model-specific:
  *   GAUSSIAN: none.  EIGHT_SCHOOLS: {J}.  KIDIQ: {N}.  DIAMONDS: {N, K}. */
