@@ -18,6 +18,7 @@
 #include "../../include/amh.h"
 #include "../../include/amh_math.h"
 #include "amh_internal.h"
+#include "amh_s64_sched.h"
 
 namespace amh {
 
@@ -229,6 +230,13 @@ int32_t step64_order(const amh_handle* h, const amh::StepParams& p) {
   return (h->s64_order >= 0 && p.in.scale == h->s64_scale && p.C == h->s64_C) ? 1 - h->s64_order : 0;
 }
 
+// ... and only such a launch has a hot part (amh_s64_sched.h): one that runs
+// ascending because it is unrelated to the previous launch finds nothing of
+// its input in the cache.
+int32_t step64_chained(const amh_handle* h, const amh::StepParams& p) {
+  return h->s64_order >= 0 && p.in.scale == h->s64_scale && p.C == h->s64_C;
+}
+
 void step64_launched(amh_handle* h, const amh::StepParams& p) {
   h->s64_scale = p.out.scale;
   h->s64_C = p.C;
@@ -346,6 +354,17 @@ int amh_step_order(amh_handle* h, int32_t* order) {
   if (int rc = enter(h, "amh_step_order", false)) return rc;
   if (!order) return fail(h, AMH_EINVAL, "amh_step_order: null argument");
   *order = h->s64_order;
+  return AMH_OK;
+}
+
+int amh_step64_schedule(int32_t n, int32_t descending, int32_t* index, int32_t* cls) {
+  if (n < 0 || (n > 0 && (!index || !cls))) return fail(nullptr, AMH_EINVAL, "amh_step64_schedule: bad arguments");
+  const amh::S64Sched s = amh::s64_sched((uint32_t)n, descending != 0, 1);
+  for (int32_t k = 0; k < n; ++k) {
+    const uint32_t v = amh::s64_draw(s, (uint32_t)k);
+    index[k] = (int32_t)v;
+    cls[k] = (int32_t)amh::s64_class(v, s.hot_lo, s.hot_n, s.tail_lo, s.tail_n);
+  }
   return AMH_OK;
 }
 
@@ -517,7 +536,10 @@ int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, con
                          return e;
                        });
   }
-  if (step64_shape(h)) p.descending = step64_order(h, p);
+  if (step64_shape(h)) {
+    p.descending = step64_order(h, p);
+    p.chained = step64_chained(h, p);
+  }
   const hipError_t e = amh::run_step(h->model_id, p, s);
   if (e != hipSuccess) return hip_fail(h, e, "amh_step");
   if (step64_shape(h)) step64_launched(h, p);
@@ -752,7 +774,10 @@ int amh_asss_step(amh_handle* h, int64_t num_chains, const amh_state* in, const 
     }
     return AMH_OK;
   }
-  if (step64_shape(h)) p.descending = step64_order(h, p);
+  if (step64_shape(h)) {
+    p.descending = step64_order(h, p);
+    p.chained = step64_chained(h, p);
+  }
   const hipError_t e = amh::run_asss_step(h->model_id, p, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(h, e, "amh_asss_step");
   if (step64_shape(h)) step64_launched(h, p);

@@ -52,6 +52,8 @@ struct StepParams {
                            // the propose pass would form it from the stored state
   int32_t descending;      // d = 64 step kernel: every block walks its chain range from the top (launch-
                            // uniform; the results do not depend on it, amh_capi.hip step64_order)
+  int32_t chained;         // ... and its input is what the previous d = 64 launch wrote, in the opposite order:
+                           // the launch has a hot part (amh_s64_sched.h)
 };
 
 struct InitParams {

@@ -20,6 +20,7 @@
 // transcendental from include/amh_math.h.  See DESIGN.md "bit spec".
 #include "amh_asss.h"
 #include "amh_device.h"
+#include "amh_s64_sched.h"
 
 #include <cstdlib>
 
@@ -836,12 +837,21 @@ __global__ void chain_keys_kernel(uint32_t key0, uint32_t key1, int64_t offset, 
 //   whose w_j is serial, still uses v_readlane.
 constexpr int kS64Waves = 16;
 // Cache policy of this kernel's factor traffic (its own: kLoadAux / kStoreAux
-// serve the other kernels).  The flush's stores are plain so that the next,
-// oppositely ordered launch finds what this one wrote last in the memory-side
-// cache; the DMA loads stay nt (read once per launch).  The other three pairs
-// lost on the kernel, though not on the probe (tools/ic_reuse.hip).
-constexpr int kS64LoadAux = 2;
-constexpr int kS64StoreAux = 0;
+// serve the other kernels), by the chain's place in the block's schedule
+// (amh_s64_sched.h): 0 plain, 2 nt.  The DMA loads are nt everywhere (read
+// once per launch; plain DMA loads lost on the kernel, for hot chains too).
+// The flush's stores are plain so that the next, oppositely ordered launch
+// finds what this one wrote last in the memory-side cache -- but for the hot
+// chains, the first of a chained launch: nothing written that early survives
+// the launch, and a store that does not allocate leaves the previous launch's
+// last writes in the cache until they are read.  Plain stores for the tail
+// alone lost, as did every other split tried (DESIGN.md 3.1 and its retired
+// table, tools/ic_reuse.hip).
+constexpr int kS64LoadAuxHot = 2, kS64LoadAuxCold = 2;
+constexpr int kS64StoreAuxHot = 2, kS64StoreAuxMid = 0, kS64StoreAuxTail = 0;
+// a drawn chain travels as its global index with the class bits above it
+constexpr int kS64TagShift = 60;
+constexpr int64_t kS64IdxMask = ((int64_t)1 << kS64TagShift) - 1;
 constexpr int kS64EB = 8;  // proposal: broadcast columns per LDS wait
 constexpr int kS64PB = 8;  // potential: columns per LDS wait
 static_assert(kS64EB == 8 && kS64PB == 8, "the batch readers (lds_ld4x2w / lds_ld4x4w) read two quarter-vectors per stream");
@@ -851,7 +861,7 @@ constexpr int kS64Z = 2080, kS64M = 2144, kS64S = 2208, kS64X = 2216;  // wave-b
 constexpr int kS64WB = kS64X + 64;            // floats per wave buffer (9,120 B): 64-float scratch
 constexpr int kS64Model = 64 * 68;            // GaussianM<64> rows (lds_bytes / 4)
 static_assert(kS64Z == 2080 && kS64S == kS64M + 64, "layout of prefetch_item<64>");
-// + 32 floats: the ticket, and slack for flush_factor's 9 KiB read of the last wave buffer
+// + 32 floats: the ticket, the hot / tail ranges after it (amh_s64_sched.h), and slack for flush_factor's 9 KiB read of the last wave buffer
 template <int WPB = kS64Waves>
 constexpr size_t s64_lds_bytes() { return ((size_t)kS64Model + (size_t)WPB * kS64WB + 32) * sizeof(float); }
 
@@ -1210,13 +1220,20 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   // 2, ... in an ascending launch, n - 1, n - 2, ..., 0 in a descending one
   // (n = the block's chain count), so that what one launch wrote last is what
   // the next one reads first and the memory-side cache still holds it
-  // (DESIGN.md 3.1).  Chains are independent: the order changes no bit.  Past
-  // the last chain the counter reads n, n + 1, ... or wraps to 2^32 - 1,
-  // 2^32 - 2, ...: either way an index >= n, "no item".
-  const uint32_t tk_step = p.descending ? ~0u : 1u;
+  // (amh_s64_sched.h).  Chains are independent: the order
+  // changes no bit.  The four words after the counter's 16 B hold the hot and
+  // the tail range for s64_class.
   const int64_t blk_lo = p.C * (int64_t)blockIdx.x / gridDim.x;  // one chain per wave
   const int64_t blk_hi = p.C * ((int64_t)blockIdx.x + 1) / gridDim.x;
-  if (threadIdx.x == 0) tick[0] = __uint_as_float(p.descending ? (uint32_t)(blk_hi - blk_lo) - 1u : 0u);
+  const uint32_t tk_step = p.descending ? ~0u : 1u;
+  if (threadIdx.x == 0) {
+    const S64Sched sch = s64_sched((uint32_t)(blk_hi - blk_lo), p.descending, p.chained);
+    tick[0] = __uint_as_float(sch.first);
+    tick[4] = __uint_as_float(sch.hot_lo);
+    tick[5] = __uint_as_float(sch.hot_n);
+    tick[6] = __uint_as_float(sch.tail_lo);
+    tick[7] = __uint_as_float(sch.tail_n);
+  }
   __syncthreads();
   const auto mctx = M::prepare(p.model, D, lane_id());
 #ifdef AMH_STAMPS
@@ -1245,12 +1262,31 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 
   const int64_t kEnd = blk_hi;  // "no item" sentinel
   const uint32_t tk_addr = lds_addr(tick);
+  // The draw and its class in lane 0's registers (they die before the
+  // readfirstlane): bits 30-31 of the word carry the class, a "no chain" value
+  // is clamped below them and stays >= n.  The result is the global chain index
+  // with the class at kS64TagShift; kEnd and -1 carry no class.
   auto ticket = [&]() -> int64_t {
     uint32_t v = 0;
     if (lane_id() == 0) {
-      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(tk_addr), "v"(tk_step) : "memory");
+      uint32x4_t_ b;
+      asm volatile("ds_add_rtn_u32 %0, %2, %3\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
+                   : "=&v"(v), "=&v"(b) : "v"(tk_addr), "v"(tk_step) : "memory");
+      const uint32_t cls = s64_class(v, b[0], b[1], b[2], b[3]);
+      v = (v < 0x3FFFFFFFu ? v : 0x3FFFFFFFu) | (cls << 30);
     }
-    return blk_lo + (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+    return (blk_lo + (int64_t)(w & 0x3FFFFFFFu)) | ((int64_t)(w >> 30) << kS64TagShift);
+  };
+  auto ix = [](int64_t t) -> int64_t { return t & kS64IdxMask; };
+  // the DMA of a drawn chain, at its class's load policy
+  auto prefetch = [&](int64_t t, int ln) {
+    if constexpr (kS64LoadAuxHot == kS64LoadAuxCold) {
+      prefetch_item<64, false, kS64LoadAuxCold>(p, ix(t), D, wb, ln);
+    } else {
+      if ((t >> kS64TagShift) & kS64Hot) prefetch_item<64, false, kS64LoadAuxHot>(p, ix(t), D, wb, ln);
+      else prefetch_item<64, false, kS64LoadAuxCold>(p, ix(t), D, wb, ln);
+    }
   };
 
   // z, loc and the scalars of chain `c` from registers
@@ -1291,7 +1327,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     static_for<D>([&](auto J) { U[J] = set_one_at<64, J>(0.0f, r); });
   };
   // the wave buffer's factor region (packed, column-major) -> chain `c` in HBM
-  auto flush_factor = [&](int64_t c) {
+  auto flush_aux = [&](int64_t c, auto AUX) {
     const Buf Lout(uniform_ptr(p.out.scale + c * P), P * 4u);
     const uint32_t la = wb_a + (uint32_t)lane_id() * 16u;
     static_for<3>([&](auto G) {  // three dwordx4 per lane in flight per wait
@@ -1301,15 +1337,27 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       static_for<3>([&](auto Q) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint32x4_t_, v[(int)Q]), Lout.rs,
                                                (int)(1024u * (3 * G + Q) + 16u * (uint32_t)lane_id()), 0,
-                                               kS64StoreAux);
+                                               (int)AUX);
       });
     });
   };
+  // ... for a drawn chain, at its class's store policy
+  auto flush_factor = [&](int64_t t) {
+    using std::integral_constant;
+    const int cls = (int)(t >> kS64TagShift);
+    if constexpr (kS64StoreAuxHot == kS64StoreAuxMid && kS64StoreAuxTail == kS64StoreAuxMid) {
+      flush_aux(ix(t), integral_constant<int, kS64StoreAuxMid>{});
+    } else {
+      if (cls & (int)kS64Hot) flush_aux(ix(t), integral_constant<int, kS64StoreAuxHot>{});
+      else if (cls & (int)kS64Tail) flush_aux(ix(t), integral_constant<int, kS64StoreAuxTail>{});
+      else flush_aux(ix(t), integral_constant<int, kS64StoreAuxMid>{});
+    }
+  };
 
   int64_t item = ticket();
-  int64_t nxt = item < kEnd ? ticket() : kEnd;
-  if (item < kEnd) prefetch_item<64, false, kS64LoadAux>(p, item, D, wb, lane_id());
-  for (; item < kEnd;) {
+  int64_t nxt = ix(item) < kEnd ? ticket() : kEnd;
+  if (ix(item) < kEnd) prefetch(item, lane_id());
+  for (; ix(item) < kEnd;) {
     int lane = lane_id();
     asm volatile("" : "+v"(lane));
     const int r = lane;
@@ -1321,9 +1369,9 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     // compute: 239 -> 236 us per launch (tools/gpu_prio.sh A/B)
     __builtin_amdgcn_s_setprio(3);
     // ---- item k-1's z / loc / scalars leave from registers
-    if (prev >= 0) store_small(prev, r);
+    if (prev >= 0) store_small(ix(prev), r);
     const bool wr = prev >= 0 && prev_upd;
-    if (prev >= 0 && !prev_upd) copy_verbatim(prev, r);
+    if (prev >= 0 && !prev_upd) copy_verbatim(ix(prev), r);
 
     // ---- diagonal of item k
     float lnew = lds_ld1<0>(wb_a + (uint32_t)s64_col(r) * 4u);
@@ -1350,7 +1398,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       s64_wr(zm_a + (uint32_t)r * 4u, dl);
       s64_wr_off<256>(zm_a + (uint32_t)r * 4u, inv);
       dl = lnew;
-      acc0 = (!kASSS && p.accept_count != nullptr && r == 0) ? p.accept_count[item] : 0;
+      acc0 = (!kASSS && p.accept_count != nullptr && r == 0) ? p.accept_count[ix(item)] : 0;
     }
 
     // ---- swap: read item k's column j (lanes > j), write item k-1's column j
@@ -1377,8 +1425,8 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 
     s64_wait();  // every LDS read of the buffer is done before the DMA refills it
     int64_t nxt2 = kEnd;
-    if (nxt < kEnd) {
-      prefetch_item<64, false, kS64LoadAux>(p, nxt, D, wb, lane);
+    if (ix(nxt) < kEnd) {
+      prefetch(nxt, lane);
       nxt2 = ticket();
     }
     __builtin_amdgcn_s_setprio(0);
@@ -1533,8 +1581,8 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       if (p.col_z != nullptr || p.col_pe != nullptr) {
         if ((t + 1) % p.thinning == 0) {
           const int64_t kk = t / p.thinning;
-          if (p.col_z != nullptr) p.col_z[(kk * C + item) * D + r] = z;
-          if (p.col_pe != nullptr && r == 0) p.col_pe[kk * C + item] = pe;
+          if (p.col_z != nullptr) p.col_z[(kk * C + ix(item)) * D + r] = z;
+          if (p.col_pe != nullptr && r == 0) p.col_pe[kk * C + ix(item)] = pe;
         }
       }
     }
@@ -1550,7 +1598,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     int lane = lane_id();
     asm volatile("" : "+v"(lane));
     const uint32_t la = wb_a + (uint32_t)lane * 4u;
-    store_small(prev, lane);
+    store_small(ix(prev), lane);
     if (prev_upd) {
       s64_wr(x_a + (uint32_t)lane * 4u, dl);
       static_for<16>([&](auto G4) {
@@ -1564,7 +1612,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       });
       flush_factor(prev);
     } else {
-      copy_verbatim(prev, lane);
+      copy_verbatim(ix(prev), lane);
     }
   }
   __builtin_amdgcn_s_waitcnt(0);

@@ -60,6 +60,7 @@ def _signatures():
         "amh_destroy": (I, [P]),
         "amh_check_device": (I, [P]),
         "amh_step_order": (I, [P, ctypes.POINTER(I32)]),
+        "amh_step64_schedule": (I, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
         "amh_bind_model": (I, [P, I32, P, I64, ctypes.POINTER(I64), I32]),
         "amh_init": (I, [P, KEY, I64, I64, P, S, P]),
         "amh_step": (I, [P, I64, S, S, I32, COL, P]),

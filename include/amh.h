@@ -135,6 +135,18 @@ int amh_check_device(amh_handle* h);
  * entry only makes the choice observable.  No counterpart in the reference. */
 int amh_step_order(amh_handle* h, int32_t* order);
 
+/* The schedule the d = 64 step kernel gives a block of n chains (host only, no
+ * device needed): index[k] is the block-local chain drawn k-th, 0 ... n - 1
+ * ascending or n - 1 ... 0 when descending is non-zero, and cls[k] its place
+ * class in a launch chained to an oppositely ordered previous launch: bit 0
+ * "hot", one of the first floor(3 n / 8) draws (what the previous launch drew
+ * last, so likely still in the memory-side cache), bit 1 "tail", one of the
+ * last floor(3 n / 8) draws (what the next launch draws first).  The class only
+ * picks the cache policy of the chain's factor traffic; an unchained launch has
+ * the same order and tail and no hot part.  Both arrays hold n entries.  No
+ * counterpart in the reference. */
+int amh_step64_schedule(int32_t n, int32_t descending, int32_t* index, int32_t* cls);
+
 /* Model plug-in (arwmh.py:109-116 / the scripts' numpyro models).
  * data: device pointer, n_data floats; iparams model-specific:
  *   GAUSSIAN: none.  EIGHT_SCHOOLS: {J}.  KIDIQ: {N}.  DIAMONDS: {N, K}. */
