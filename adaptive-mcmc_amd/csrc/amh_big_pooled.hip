@@ -1992,7 +1992,7 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* pack, double*
       hipLaunchKernelGGL(pooled_fused64_kernel<false>, dim3((unsigned)grid), dim3(256), fused64_lds_bytes(), s, p, nch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (p.defer_reduce) return hipSuccess;  // the update launch reduces (run_pooled_big_update)
+    if (p.defer_reduce || sums == nullptr) return hipSuccess;  // the update launch reduces (run_pooled_big_update)
     return launch_reduce_tiles((const float*)p.partials, nch, pooled_big_tile_V(d), sums, p.accumulate, d, FinalPrep{},
                                s);
   }
@@ -2020,7 +2020,7 @@ hipError_t run_pooled_big_stats(const PooledStatsParams& p, float* pack, double*
         return hipErrorInvalidValue;
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || sums == nullptr) return e;
     // one launch (was pooled_group4_kernel + pooled_final_kernel)
     return launch_reduce_tiles((const float*)p.partials, nch, pooled_big_tile_V(d), sums, p.accumulate, d, p.prep, s);
   }

@@ -17,6 +17,7 @@
 
 #include "../../include/amh.h"
 #include "../../include/amh_math.h"
+#include "amh_exact.h"
 #include "amh_internal.h"
 #include "amh_s64_sched.h"
 
@@ -898,18 +899,55 @@ struct DeferredReduce {
   int32_t accumulate = 0;
 };
 
+// exact sums: the chunk a rank must be aligned to, from the chain count of all
+// ranks.  The lane-per-row form cuts 16 pooled_cpw(total) chains, the MFMA
+// form 128; d = 64 has both (the Gaussian and a caller's potential on MFMA,
+// the other registry models lane per row), and a multiple of either serves
+int64_t exact_chunk_chains(int d, int64_t total_chains) {
+  const int64_t lane = (int64_t)amh::kPoolWaves * amh::pooled_cpw(total_chains);
+  if (d < 64) return lane;
+  if (d > 64) return 128;
+  int64_t m = 128;
+  while (m % lane != 0) m += 128;
+  return m;
+}
+
+// the entry's partial rows, as the stats launch has just left them, into the
+// exact words
+int exact_reduce(amh_handle* h, int64_t n_chunks, bool big, int64_t* acc, int accumulate, void* stream,
+                 const char* who) {
+  const int d = h->cfg.dim;
+  const int64_t vrow = big ? amh::pooled_big_tile_V(d) : amh::pooled_sums_len(d);
+  const hipError_t e = amh::run_pooled_exact_reduce(h->partials.ptr, big, n_chunks, vrow, big ? d : 0, acc, accumulate,
+                                                    (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "(exact reduce)");
+  return AMH_OK;
+}
+
 // prep_for_update: the update follows in the same library call with no
 // exchange in between (amh_pooled_step_k on one rank), so the large-d
-// reduction's last kernel also forms that update's Sigma'
+// reduction's last kernel also forms that update's Sigma'.
+// exact_acc: the partial rows go to the exact words there instead of `sums`
+// (unused), the lane-per-row chunks cut by total_chains, the chains of all ranks
 int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps, float* z_out,
                       float* pe_out, double* sums, void* stream, bool prep_for_update, bool* sigma_ready,
-                      DeferredReduce* deferred = nullptr, bool pack_ready = false) {
-  const char* const who = "amh_pooled_stats";
+                      DeferredReduce* deferred = nullptr, bool pack_ready = false, int64_t* exact_acc = nullptr,
+                      int64_t total_chains = 0) {
+  const char* const who = exact_acc ? "amh_pooled_stats_k_exact" : "amh_pooled_stats";
   if (sigma_ready) *sigma_ready = false;
   if (deferred) *deferred = DeferredReduce{};
   if (int rc = enter(h, who, true)) return rc;
-  if (!pooled_ok(in) || !z_out || !pe_out || !sums || num_chains < 1 || k_steps < 1)
-    return fail(h, AMH_EINVAL, "amh_pooled_stats: bad arguments");
+  if (!pooled_ok(in) || !z_out || !pe_out || (!sums && !exact_acc) || num_chains < 1 || k_steps < 1)
+    return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  if (exact_acc) {
+    sums = nullptr;
+    if (total_chains < num_chains) return fail(h, AMH_EINVAL, std::string(who) + ": total_chains < num_chains");
+    // N of a chunk, k_steps * its chains, must be a float32 value like every other partial
+    if ((int64_t)k_steps * amh::kPoolWaves * 16 > ((int64_t)1 << 24))
+      return fail(h, AMH_EINVAL, std::string(who) + ": k_steps too large for exact sums");
+  } else {
+    total_chains = num_chains;
+  }
   if (int rc = check_device_flag(h)) return rc;
   if (int rc = use_device(h, who)) return rc;
   const int d = h->cfg.dim;
@@ -917,12 +955,13 @@ int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state*
   if (d > 64 && !big) return fail(h, AMH_EINVAL, "amh_pooled_stats: d > 64 needs d % 32 == 0 in the pooled mode");
   if (h->model_id == AMH_MODEL_EXTERNAL)
     return fail(h, AMH_EINVAL, "amh_pooled_stats: the pooled mode needs a device potential (not external)");
-  const int cpw = amh::pooled_cpw(num_chains);
+  const int cpw = amh::pooled_cpw(total_chains);
   const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
   const int64_t n_chunks = big ? amh::pooled_big_chunks(num_chains, d) : (num_chains + chunk - 1) / chunk;
   if (int rc = reserve_partials(h, n_chunks, big, stream, who)) return rc;
   amh::PooledStatsParams p{};
   p.C = num_chains;
+  p.cpw = cpw;
   p.d = d;
   p.i = in->i;
   p.z = in->z;
@@ -940,7 +979,7 @@ int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state*
   if (!big) {
     const hipError_t e = amh::run_pooled_stats(h->model_id, p, sums, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats");
-    return AMH_OK;
+    return exact_acc ? exact_reduce(h, n_chunks, false, exact_acc, 0, stream, who) : AMH_OK;
   }
   // the fused path's A-operand copies
   h->big_ready_C = -1;
@@ -991,6 +1030,8 @@ int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state*
     }
     const hipError_t e = amh::run_pooled_big_stats(p, h->split.as<float>(), sums, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats(MFMA path)");
+    if (exact_acc)
+      if (int rc = exact_reduce(h, n_chunks, true, exact_acc, p.accumulate, stream, who)) return rc;
     p.pack_ready = 1;  // the K steps of a pooled block share the frozen factor
   }
   return AMH_OK;
@@ -1077,7 +1118,25 @@ int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled_state*
   p->L = in->scale;
   p->lam = in->log_step_size;
   p->eps = h->cfg.eps;
+  p->cpw = amh::pooled_cpw(num_chains);
   return AMH_OK;
+}
+
+// the accept pass of `p` and its sums: the double reduction into `sums`, or
+// (acc non-null) the partial rows into the exact words
+int pooled_ext_stats(amh_handle* h, amh::PooledExtParams& p, const float* zprop, const float* pe_prop, float* z_out,
+                     float* pe_out, double* sums, int64_t* acc, int32_t accumulate, void* stream, const char* who) {
+  const bool big = amh::pooled_big_model(h->model_id, p.d);
+  const int64_t n_chunks = amh::pooled_ext_chunks(p.C, p.d, p.cpw);
+  if (int rc = reserve_partials(h, n_chunks, big, stream, who)) return rc;
+  p.zprop = const_cast<float*>(zprop);
+  p.pe_prop = pe_prop;
+  p.z_out = z_out;
+  p.pe_out = pe_out;
+  p.partials = h->partials.as<double>();
+  const hipError_t e = amh::run_pooled_ext_stats(p, acc ? nullptr : sums, accumulate != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return acc ? exact_reduce(h, n_chunks, big, acc, accumulate != 0, stream, who) : AMH_OK;
 }
 
 // ncclAllReduce / ncclGetErrorString of the RCCL instance already in the
@@ -1093,6 +1152,23 @@ void* rccl_handle() {
     if (hd == nullptr) hd = dlopen("librccl.so.1", RTLD_NOW);
   }
   return hd;
+}
+
+// in-place ncclAllReduce(sum) of n elements of RCCL type `dtype`, as the entry `who`
+int pooled_allreduce(amh_handle* h, void* buf, int64_t n, int dtype, void* rccl_comm, void* stream, const char* who) {
+  if (int rc = enter(h, who, false)) return rc;
+  if (!buf || !rccl_comm || n < 0) return fail(h, AMH_EINVAL, std::string(who) + ": null sums / communicator");
+  void* hd = rccl_handle();
+  auto ar = hd ? (nccl_allreduce_fn)dlsym(hd, "ncclAllReduce") : nullptr;
+  if (ar == nullptr) return fail(h, AMH_EHIP, std::string(who) + ": librccl not found");
+  constexpr int kNcclSum = 0;
+  const int rc = ar(buf, buf, (size_t)n, dtype, kNcclSum, rccl_comm, stream);
+  if (rc != 0) {
+    auto es = (nccl_errstr_fn)dlsym(hd, "ncclGetErrorString");
+    return fail(h, AMH_EHIP, std::string(who) + ": ncclAllReduce: " + (es ? es(rc) : "error") + " (ncclResult " +
+                                 std::to_string(rc) + ")");
+  }
+  return AMH_OK;
 }
 
 }  // namespace
@@ -1175,31 +1251,80 @@ int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_poole
   if (!zprop || !pe_prop || !z_out || !pe_out || !sums)
     return fail(h, AMH_EINVAL, "amh_pooled_stats_external: bad arguments");
   if (int rc = use_device(h, who)) return rc;
-  if (int rc = reserve_partials(h, amh::pooled_ext_chunks(num_chains, p.d), amh::pooled_big_model(h->model_id, p.d),
-                             stream, who))
-    return rc;
-  p.zprop = const_cast<float*>(zprop);
-  p.pe_prop = pe_prop;
-  p.z_out = z_out;
-  p.pe_out = pe_out;
-  p.partials = h->partials.as<double>();
-  const hipError_t e = amh::run_pooled_ext_stats(p, sums, accumulate != 0, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(h, e, "amh_pooled_stats_external");
-  return AMH_OK;
+  return pooled_ext_stats(h, p, zprop, pe_prop, z_out, pe_out, sums, nullptr, accumulate, stream, who);
+}
+
+int amh_pooled_stats_external_exact(amh_handle* h, int64_t num_chains, int64_t total_chains,
+                                    const amh_pooled_state* in, int32_t t, const float* zprop, const float* pe_prop,
+                                    float* z_out, float* pe_out, int64_t* acc, int32_t accumulate, void* stream) {
+  const char* const who = "amh_pooled_stats_external_exact";
+  amh::PooledExtParams p;
+  if (int rc = pooled_ext_params(h, num_chains, in, t, who, &p)) return rc;
+  if (!zprop || !pe_prop || !z_out || !pe_out || !acc || total_chains < num_chains)
+    return fail(h, AMH_EINVAL, "amh_pooled_stats_external_exact: bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  p.cpw = amh::pooled_cpw(total_chains);
+  return pooled_ext_stats(h, p, zprop, pe_prop, z_out, pe_out, nullptr, acc, accumulate, stream, who);
 }
 
 int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm, void* stream) {
-  if (int rc = enter(h, "amh_pooled_allreduce", false)) return rc;
-  if (!sums || !rccl_comm || n < 0) return fail(h, AMH_EINVAL, "amh_pooled_allreduce: null sums / communicator");
-  void* hd = rccl_handle();
-  auto ar = hd ? (nccl_allreduce_fn)dlsym(hd, "ncclAllReduce") : nullptr;
-  if (ar == nullptr) return fail(h, AMH_EHIP, "amh_pooled_allreduce: librccl not found");
-  constexpr int kNcclFloat64 = 8, kNcclSum = 0;
-  const int rc = ar(sums, sums, (size_t)n, kNcclFloat64, kNcclSum, rccl_comm, stream);
-  if (rc != 0) {
-    auto es = (nccl_errstr_fn)dlsym(hd, "ncclGetErrorString");
-    return fail(h, AMH_EHIP, std::string("amh_pooled_allreduce: ncclAllReduce: ") + (es ? es(rc) : "error") +
-                                 " (ncclResult " + std::to_string(rc) + ")");
+  constexpr int kNcclFloat64 = 8;
+  return pooled_allreduce(h, sums, n, kNcclFloat64, rccl_comm, stream, "amh_pooled_allreduce");
+}
+
+int amh_pooled_allreduce_i64(amh_handle* h, int64_t* acc, int64_t n, void* rccl_comm, void* stream) {
+  constexpr int kNcclInt64 = 4;
+  return pooled_allreduce(h, acc, n, kNcclInt64, rccl_comm, stream, "amh_pooled_allreduce_i64");
+}
+
+int amh_pooled_exact_size(int32_t dim, int64_t* n) {
+  if (dim < 1 || dim > 256 || !n) return fail(nullptr, AMH_EINVAL, "amh_pooled_exact_size: bad arguments");
+  *n = amh::pooled_sums_len(dim) * amh::kExactWords;
+  return AMH_OK;
+}
+
+int amh_pooled_chunk_chains(int32_t dim, int64_t total_chains, int64_t* n) {
+  if (dim < 1 || dim > 256 || (dim > 64 && dim % 32 != 0) || total_chains < 1 || !n)
+    return fail(nullptr, AMH_EINVAL, "amh_pooled_chunk_chains: bad arguments");
+  *n = exact_chunk_chains(dim, total_chains);
+  return AMH_OK;
+}
+
+int amh_pooled_stats_k_exact(amh_handle* h, int64_t num_chains, int64_t total_chains, const amh_pooled_state* in,
+                             int32_t k_steps, float* z_out, float* pe_out, int64_t* acc, void* stream) {
+  if (h && !acc) return fail(h, AMH_EINVAL, "amh_pooled_stats_k_exact: bad arguments");
+  return pooled_stats_impl(h, num_chains, in, k_steps, z_out, pe_out, nullptr, stream, false, nullptr, nullptr, false,
+                           acc, total_chains);
+}
+
+int amh_pooled_exact_to_sums(amh_handle* h, const int64_t* acc, double* sums, void* stream) {
+  const char* const who = "amh_pooled_exact_to_sums";
+  if (int rc = enter(h, who, false)) return rc;
+  if (!acc || !sums) return fail(h, AMH_EINVAL, "amh_pooled_exact_to_sums: bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  const hipError_t e = amh::run_pooled_exact_convert(acc, amh::pooled_sums_len(h->cfg.dim), sums, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+int amh_pooled_exact_quantise(const float* partials, int64_t rows, int64_t v, int64_t* acc, int32_t accumulate) {
+  if (rows < 0 || v < 0 || !acc || (rows > 0 && v > 0 && !partials))
+    return fail(nullptr, AMH_EINVAL, "amh_pooled_exact_quantise: bad arguments");
+  for (int64_t c = 0; c < v; ++c) {
+    int64_t w[amh::kExactWords];
+    for (int j = 0; j < amh::kExactWords; ++j) w[j] = accumulate ? acc[c * amh::kExactWords + j] : 0;
+    for (int64_t r = 0; r < rows; ++r) amh::exact_add(w, partials[r * v + c]);
+    for (int j = 0; j < amh::kExactWords; ++j) acc[c * amh::kExactWords + j] = w[j];
+  }
+  return AMH_OK;
+}
+
+int amh_pooled_exact_to_double(const int64_t* acc, int64_t v, double* out) {
+  if (v < 0 || (v > 0 && (!acc || !out))) return fail(nullptr, AMH_EINVAL, "amh_pooled_exact_to_double: bad arguments");
+  for (int64_t c = 0; c < v; ++c) {
+    int64_t w[amh::kExactWords];
+    for (int j = 0; j < amh::kExactWords; ++j) w[j] = acc[c * amh::kExactWords + j];
+    out[c] = amh::exact_to_double(w);
   }
   return AMH_OK;
 }

@@ -158,6 +158,10 @@ struct PooledStatsParams {
   // d > 64: the A-operand copies are current (the previous update's post
   // kernel wrote the factor's tiles; the precision's are from the first pack)
   int32_t pack_ready;
+  // d <= 64, lane-per-row form: chains each wave of a chunk takes.
+  // pooled_cpw(C), or with exact sums pooled_cpw of the chain count of all
+  // ranks, so that every rank cuts the same chunks (amh_pooled_stats_k_exact)
+  int32_t cpw;
 };
 
 // Pool-every-K: the update after a block of K transitions that started at
@@ -198,6 +202,8 @@ struct PooledUpdateParams {
 };
 int pooled_reduce64_blocks(int64_t V);  // reduce blocks of the d = 64 partial rows
 
+// sums == nullptr (here, run_pooled_big_stats and run_pooled_ext_stats): the
+// chunk partial rows are left unreduced for run_pooled_exact_reduce
 hipError_t run_pooled_stats(int model_id, const PooledStatsParams& p, double* sums, hipStream_t s);
 // large dimensions (amh_big_pooled.hip): chunks of 256 chains
 int64_t pooled_big_chunks(int64_t C, int d);
@@ -230,10 +236,18 @@ struct PooledExtParams {
   const float* pe_prop;  // [C] (stats)
   float *z_out, *pe_out; // (stats; may alias z / pe)
   double* partials;      // (stats) chunk partial rows + the reduction's scratch
+  int32_t cpw;           // (stats, d < 64) chains per wave of a chunk, as PooledStatsParams::cpw
 };
-int64_t pooled_ext_chunks(int64_t C, int d);
+int64_t pooled_ext_chunks(int64_t C, int d, int cpw);
 hipError_t run_pooled_ext_propose(const PooledExtParams& p, hipStream_t s);
 hipError_t run_pooled_ext_stats(const PooledExtParams& p, double* sums, int accumulate, hipStream_t s);
+// exact sums (amh_pooled_exact.hip, amh_exact.h): a rank's chunk partial rows
+// (f32_rows: float32 rows in the tile layout of d = tile_d, else double rows
+// of the sums' own layout, tile_d = 0) -> acc [V][kExactWords] int64
+// (accumulate: acc += them), and the words -> the V doubles of the sums
+hipError_t run_pooled_exact_reduce(const void* partials, bool f32_rows, int64_t n_chunks, int64_t Vrow, int tile_d,
+                                   int64_t* acc, int accumulate, hipStream_t s);
+hipError_t run_pooled_exact_convert(const int64_t* acc, int64_t V, double* sums, hipStream_t s);
 hipError_t run_asss_step(int model_id, const StepParams& p, hipStream_t s);  // amh_asss.hip
 hipError_t run_asss_step64(const StepParams& p, hipStream_t s);  // amh_kernels.hip (d = 64 Gaussian)
 hipError_t run_asss_pnx(int model_id, const AsssPnxParams& p, hipStream_t s);

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_stats_kernel(PooledSta
   const float mu = act ? p.mu[r] : 0.0f;
   const uint32_t prow = lds_addr(lrow + (act ? r : 0) * ld);
 
-  const int cpw = pooled_cpw(p.C);
+  const int cpw = p.cpw;
   const int64_t chunk0 = (int64_t)blockIdx.x * kPoolWaves * cpw;
   const int64_t base = chunk0 + (int64_t)w * cpw;
   float S[64];
@@ -333,13 +333,13 @@ hipError_t launch_pooled_stats(const PooledStatsParams& p, double* sums, hipStre
   const int d = EXACT ? 64 : p.d;
   const size_t shm = pooled_lds_bytes<M>(p.model, d);
   if (shm > 163840) return hipErrorInvalidConfiguration;
-  const int cpw = pooled_cpw(p.C);
+  const int cpw = p.cpw;
   const int64_t chunk = (int64_t)kPoolWaves * cpw;
   const int64_t n_chunks = (p.C + chunk - 1) / chunk;
   const int64_t V = pooled_sums_len(d);
   hipLaunchKernelGGL((pooled_stats_kernel<M, EXACT>), dim3((unsigned)n_chunks), dim3(kPoolWaves * 64), shm, s, p);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess || sums == nullptr) return e;
   return pooled_reduce(p.partials, n_chunks, V, sums, 0, s);
 }
 

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_ext_stats_kernel(Poole
   const int32_t it = __builtin_amdgcn_readfirstlane(p.i[0] + p.t);
   const float mu = act ? p.mu[r] : 0.0f;
 
-  const int cpw = pooled_cpw(p.C);
+  const int cpw = p.cpw;
   const int64_t chunk0 = (int64_t)blockIdx.x * kPoolWaves * cpw;
   const int64_t base = chunk0 + (int64_t)w * cpw;
   const int64_t end = (base + cpw < p.C) ? base + cpw : p.C;
@@ -392,22 +392,22 @@ hipError_t run_pooled_ext_propose(const PooledExtParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-int64_t pooled_ext_chunks(int64_t C, int d) {
+int64_t pooled_ext_chunks(int64_t C, int d, int cpw) {
   if (ext_big(d)) return (C + kChunk - 1) / kChunk;
-  const int64_t chunk = (int64_t)kPoolWaves * pooled_cpw(C);
+  const int64_t chunk = (int64_t)kPoolWaves * cpw;
   return (C + chunk - 1) / chunk;
 }
 
 hipError_t run_pooled_ext_stats(const PooledExtParams& p, double* sums, int accumulate, hipStream_t s) {
   const int d = p.d;
   if (d < 1 || (d > 64 && !ext_big(d))) return hipErrorInvalidValue;
-  const int64_t n_chunks = pooled_ext_chunks(p.C, d);
+  const int64_t n_chunks = pooled_ext_chunks(p.C, d, p.cpw);
   if (!ext_big(d)) {
     const int64_t V = pooled_sums_len(d);
     hipLaunchKernelGGL(pooled_ext_stats_kernel, dim3((unsigned)n_chunks), dim3(kPoolWaves * 64),
                        kPooledTreeFloats * sizeof(float), s, p);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || sums == nullptr) return e;
     return pooled_reduce(p.partials, n_chunks, V, sums, accumulate, s);
   }
   const int64_t cap = (int64_t)device_cus();
@@ -424,7 +424,7 @@ hipError_t run_pooled_ext_stats(const PooledExtParams& p, double* sums, int accu
       return hipErrorInvalidValue;
   }
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess || sums == nullptr) return e;
   return launch_reduce_tiles((const float*)p.partials, n_chunks, pooled_big_tile_V(d), sums, accumulate, d, FinalPrep{},
                              s);
 }

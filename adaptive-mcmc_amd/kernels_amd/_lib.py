@@ -93,6 +93,15 @@ def _signatures():
         "amh_pooled_allreduce": (I, [P, P, I64, P, P]),
         "amh_pooled_propose": (I, [P, I64, PS, I32, P, P]),
         "amh_pooled_stats_external": (I, [P, I64, PS, I32, P, P, P, P, P, I32, P]),
+        # pooled covariance, exact sums
+        "amh_pooled_exact_size": (I, [I32, ctypes.POINTER(I64)]),
+        "amh_pooled_chunk_chains": (I, [I32, I64, ctypes.POINTER(I64)]),
+        "amh_pooled_stats_k_exact": (I, [P, I64, I64, PS, I32, P, P, P, P]),
+        "amh_pooled_stats_external_exact": (I, [P, I64, I64, PS, I32, P, P, P, P, P, I32, P]),
+        "amh_pooled_exact_to_sums": (I, [P, P, P, P]),
+        "amh_pooled_allreduce_i64": (I, [P, P, I64, P, P]),
+        "amh_pooled_exact_quantise": (I, [P, I64, I64, P, I32]),
+        "amh_pooled_exact_to_double": (I, [P, I64, P]),
     }
 
 

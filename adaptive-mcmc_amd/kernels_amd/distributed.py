@@ -17,13 +17,33 @@ import torch
 import torch.distributed as dist
 
 
-def shard_range(num_chains: int, rank: int, world: int) -> Tuple[int, int]:
+def shard_range(num_chains: int, rank: int, world: int, align: int = 1) -> Tuple[int, int]:
     """(offset, count) of rank's contiguous block of global chain ids; the
-    first num_chains % world ranks get one extra chain."""
+    first num_chains % world ranks get one extra chain.
+
+    align = a > 1 (PooledARWMH(exact_sums=True): a = pooled_chunk(d,
+    num_chains)) hands out whole runs of a chains instead: the
+    ceil(num_chains / a) chunks are spread the same way (the first
+    n_chunks % world ranks get one extra chunk), every offset is a multiple
+    of a, and the ragged tail of the last chunk belongs to the last rank.
+    ValueError when there are fewer chunks than ranks (a rank would be
+    empty)."""
     if world < 1 or not 0 <= rank < world:
         raise ValueError(f"bad rank {rank} of world {world}")
     if num_chains < 0:
         raise ValueError("num_chains must be >= 0")
+    if int(align) < 1:
+        raise ValueError("align must be >= 1")
+    if int(align) > 1:
+        a = int(align)
+        n_chunks = -(-num_chains // a)
+        if n_chunks < world:
+            raise ValueError(f"{num_chains} chains are {n_chunks} chunks of {a}: rank(s) of a world of {world} "
+                             f"would be empty")
+        base, extra = divmod(n_chunks, world)
+        offset = (rank * base + min(rank, extra)) * a
+        count = (base + (1 if rank < extra else 0)) * a
+        return offset, min(count, num_chains - offset)
     base, extra = divmod(num_chains, world)
     count = base + (1 if rank < extra else 0)
     offset = rank * base + min(rank, extra)
@@ -202,15 +222,19 @@ class RcclComm:
         (default: the current stream of buf's device).  With a library
         `handle` (kernels_amd._lib.Handle) and float64 sums the call goes
         through the C ABI's amh_pooled_allreduce (include/amh.h), the entry a
-        non-Python binding uses; otherwise through ctypes into librccl."""
-        if handle is not None and buf.dtype == torch.float64 and buf.is_cuda and buf.is_contiguous():
+        non-Python binding uses, and with the int64 words of the exact sums
+        through amh_pooled_allreduce_i64; otherwise through ctypes into
+        librccl."""
+        if (handle is not None and buf.dtype in (torch.float64, torch.int64) and buf.is_cuda
+                and buf.is_contiguous()):
             from . import _lib
             s = stream if stream is not None else torch.cuda.current_stream(buf.device)
             L = _lib.lib()
-            rc = L.amh_pooled_allreduce(handle.h, buf.data_ptr(), buf.numel(), self.ptr, s.cuda_stream)
+            entry = "amh_pooled_allreduce" if buf.dtype == torch.float64 else "amh_pooled_allreduce_i64"
+            rc = getattr(L, entry)(handle.h, buf.data_ptr(), buf.numel(), self.ptr, s.cuda_stream)
             if rc != 0:
                 msg = L.amh_last_error(handle.h)
-                raise RcclError(msg.decode() if msg else f"amh_pooled_allreduce: {rc}")
+                raise RcclError(msg.decode() if msg else f"{entry}: {rc}")
             return
         rccl_allreduce_sum(buf, self.ptr, stream)
 

@@ -40,6 +40,23 @@ def sums_size(d: int) -> int:
     return d + packed_size(d) + 2
 
 
+def pooled_chunk(dim: int, total_chains: int) -> int:
+    """Chains per chunk of the pooled sums in a run of `total_chains` chains
+    over all ranks (amh_pooled_chunk_chains): with exact_sums=True every
+    rank's chain_offset must be a multiple, e.g. from
+    distributed.shard_range(total_chains, rank, world, align=pooled_chunk(...))."""
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.lib().amh_pooled_chunk_chains(int(dim), int(total_chains), ctypes.byref(n)))
+    return n.value
+
+
+def exact_size(d: int) -> int:
+    """int64 words of the exact sums (amh_pooled_exact_size)."""
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.lib().amh_pooled_exact_size(int(d), ctypes.byref(n)))
+    return n.value
+
+
 class PooledARWMH(ARWMH):
     """ARWMH with one adapt state shared by every chain (and every rank).
 
@@ -83,13 +100,24 @@ class PooledARWMH(ARWMH):
     from); only which sums it consumes differs, so this is a delayed
     stochastic-approximation step.  The sums of the last block stay pending
     in the sampler and are applied by the next call.  Results do not depend on
-    the rank count (up to the association order of the sums across ranks)."""
+    the rank count (up to the association order of the sums across ranks).
+
+    exact_sums = True removes that parenthesis: every chunk partial of the
+    stats kernels is mapped to fixed-point int64 limbs (include/amh.h "exact
+    sums"), integers are all that is added -- within a rank, over the steps of
+    a block and in the all-reduce -- and the totals are rounded to the usual
+    float64 sums once, after the exchange.  A run is then byte-identical for
+    every rank count whose shards start at multiples of
+    pooled_chunk(d, total chains) (init raises ValueError otherwise;
+    distributed.shard_range(..., align=) makes such shards), one rank
+    included; it differs from the default run as two association orders do.
+    The message grows from 8 to 40 bytes per component."""
 
     pooled = True  # adapt-state leaves carry no chain axis
 
     def __init__(self, model=None, potential_fn=None, lr_decay=2 / 3, target_accept_prob=0.234, eps=1e-6,
                  num_chains=None, device=None, chain_offset=0, group=None, sync_every: int = 1,
-                 overlap: bool = False, **kw):
+                 overlap: bool = False, exact_sums: bool = False, **kw):
         super().__init__(model=model, potential_fn=potential_fn, lr_decay=lr_decay,
                          target_accept_prob=target_accept_prob, eps=eps, num_chains=num_chains, device=device,
                          chain_offset=chain_offset, **kw)
@@ -103,6 +131,9 @@ class PooledARWMH(ARWMH):
         self._comm = None
         self.sync_every = int(sync_every)
         self.overlap = bool(overlap)
+        self.exact_sums = bool(exact_sums)
+        self._acc = None   # exact_sums: the int64 words of each sums buffer
+        self._total = None  # exact_sums: chains of all ranks (cuts the chunks below d = 64)
         # testing / profiling: run the multi-rank step (stats launch, the
         # all-reduce on the side stream, update launch) even in a world of one
         # rank, so the RCCL branch can be exercised and timed on one GPU
@@ -134,10 +165,26 @@ class PooledARWMH(ARWMH):
         adapt = PooledAdaptState(torch.zeros(d, **f), cov.to(torch.float32), torch.zeros(1, **f))
         self._bufs = torch.zeros(2, sums_size(d), dtype=torch.float64, device=dev)
         self._sums = self._bufs[0]
+        if self.exact_sums:
+            self._total = self._total_chains(st.z.shape[0], dev)
+            chunk = pooled_chunk(d, self._total)
+            if self._chain_offset % chunk != 0:
+                raise ValueError(f"exact_sums needs chain_offset ({self._chain_offset}) to be a multiple of the "
+                                 f"chunk of {chunk} chains (pooled_chunk({d}, {self._total}))")
+            self._acc = torch.zeros(2, exact_size(d), dtype=torch.int64, device=dev)
         self._pending = None
         self._last_out = None
         return PooledState(torch.zeros(1, dtype=torch.int32, device=dev), st.z, st.potential_energy,
                            torch.zeros(1, **f), adapt, torch.zeros(1, **f), st.rng_key, cov)
+
+    def _total_chains(self, local: int, dev) -> int:
+        """The chain count of all ranks: one all-reduce of the local counts."""
+        if self._world() == 1:
+            return int(local)
+        on_dev = dist.get_backend(self._group) == "nccl"
+        t = torch.tensor([int(local)], dtype=torch.int64, device=dev if on_dev else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._group)
+        return int(t.item())
 
     @staticmethod
     def _c(s: PooledState) -> AmhPooledState:
@@ -171,18 +218,38 @@ class PooledARWMH(ARWMH):
                            torch.empty_like(s.as_change), s.rng_key, torch.empty_like(s.cov))
 
     # ------------------------------------------------------- the exchange --
-    def _allreduce(self, buf: torch.Tensor, dev: int):
+    def _exchange(self, b: int, dev: int):
+        """The exchange of sums buffer b; returns what _allreduce does.
+        exact_sums: the all-reduce carries the buffer's int64 words, and the
+        conversion to the float64 sums follows it on the stream where it
+        completes, in every world (so one rank and N ranks run the same
+        arithmetic)."""
+        if not self.exact_sums:
+            return self._allreduce(self._bufs[b], dev)
+
+        def convert():
+            _lib.check(_lib.lib().amh_pooled_exact_to_sums(self._handle.h, _lib.ptr(self._acc[b]),
+                                                           _lib.ptr(self._bufs[b]), _lib.stream_ptr(dev)),
+                       self._handle.h)
+        return self._allreduce(self._acc[b], dev, then=convert)
+
+    def _allreduce(self, buf: torch.Tensor, dev: int, then=None):
         """all_reduce(sum) of one sums buffer.  RCCL without overlap: on the
         compute stream itself (kernels_amd.distributed.rccl_allreduce_sum:
         the update follows in stream order, no cross-stream event); returns
         None.  RCCL with overlap: enqueued on the side stream after the
         compute stream's work so far; returns the event the consumer waits
         on.  gloo (ranks sharing a device, CPU tests): done in place,
-        host-synchronous; returns None."""
+        host-synchronous; returns None.  `then` (exact_sums: the conversion) is
+        called where the reduced buffer is next available in stream order:
+        on the current stream, or on the side stream before the event."""
+        then = then or (lambda: None)
         if self._world() == 1 and not (self.force_collective and dist.is_available() and dist.is_initialized()):
+            then()
             return None
         if dist.get_backend(self._group) != "nccl":
             dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self._group)
+            then()
             return None
         if not self.overlap and not self.torch_stream_collective:
             # this package's own communicator (distributed.RcclComm), the
@@ -201,12 +268,14 @@ class PooledARWMH(ARWMH):
                     self.torch_stream_collective = True
             if self._rccl_comm is not None:
                 self._rccl_comm.all_reduce_sum(buf, torch.cuda.current_stream(dev), handle=self._handle)
+                then()
                 return None
         if self._comm is None:
             self._comm = torch.cuda.Stream(device=dev)
         self._comm.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self._comm):
             dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self._group)
+            then()
             ev = torch.cuda.Event()
             ev.record(self._comm)
         return ev
@@ -219,7 +288,7 @@ class PooledARWMH(ARWMH):
             c, self._rccl_comm = self._rccl_comm, None
             c.close()
 
-    def _stats_external(self, L, cin, sout, buf, C):
+    def _stats_external(self, L, cin, sout, b, C):
         """AMH_MODEL_EXTERNAL: the block's K transitions as K rounds of
         amh_pooled_propose, the caller's U of the proposals, and
         amh_pooled_stats_external (accept + the round's sums, added to the
@@ -232,20 +301,32 @@ class PooledARWMH(ARWMH):
         for t in range(self.sync_every):
             _lib.check(L.amh_pooled_propose(h, C, ctypes.byref(cur), t, _lib.ptr(zp), st), h)
             pe = self._potential_fn.evaluate(zp)
-            _lib.check(L.amh_pooled_stats_external(h, C, ctypes.byref(cur), t, _lib.ptr(zp), _lib.ptr(pe),
-                                                   _lib.ptr(sout.z), _lib.ptr(sout.potential_energy), _lib.ptr(buf),
-                                                   int(t > 0), st), h)
+            out = (_lib.ptr(zp), _lib.ptr(pe), _lib.ptr(sout.z), _lib.ptr(sout.potential_energy))
+            if self.exact_sums:  # (integer words: the order of the rounds no longer matters)
+                rc = L.amh_pooled_stats_external_exact(h, C, self._total, ctypes.byref(cur), t, *out,
+                                                       _lib.ptr(self._acc[b]), int(t > 0), st)
+            else:
+                rc = L.amh_pooled_stats_external(h, C, ctypes.byref(cur), t, *out, _lib.ptr(self._bufs[b]),
+                                                 int(t > 0), st)
+            _lib.check(rc, h)
             if t == 0 and self.sync_every > 1:
                 cur = AmhPooledState.from_buffer_copy(cin)
                 cur.z, cur.potential_energy = sout.z.data_ptr(), sout.potential_energy.data_ptr()
 
-    def _stats(self, L, cin, sout, buf, C):
+    def _stats(self, L, cin, sout, b, C):
+        """The block's transitions and this rank's sums into buffer b (its
+        float64 sums, or with exact_sums its int64 words)."""
         dev = sout.z.device.index
         if self._external():
-            return self._stats_external(L, cin, sout, buf, C)
+            return self._stats_external(L, cin, sout, b, C)
+        if self.exact_sums:
+            _lib.check(L.amh_pooled_stats_k_exact(self._handle.h, C, self._total, ctypes.byref(cin), self.sync_every,
+                                                  _lib.ptr(sout.z), _lib.ptr(sout.potential_energy),
+                                                  _lib.ptr(self._acc[b]), _lib.stream_ptr(dev)), self._handle.h)
+            return
         _lib.check(L.amh_pooled_stats_k(self._handle.h, C, ctypes.byref(cin), self.sync_every, _lib.ptr(sout.z),
-                                        _lib.ptr(sout.potential_energy), _lib.ptr(buf), _lib.stream_ptr(dev)),
-                   self._handle.h)
+                                        _lib.ptr(sout.potential_energy), _lib.ptr(self._bufs[b]),
+                                        _lib.stream_ptr(dev)), self._handle.h)
 
     def _update(self, L, buf, cin, cout):
         dev = buf.device.index
@@ -260,8 +341,8 @@ class PooledARWMH(ARWMH):
         with torch.cuda.device(dev):
             if not self.overlap:
                 buf = self._bufs[0]
-                self._stats(L, cin, sout, buf, C)
-                ev = self._allreduce(buf, dev)
+                self._stats(L, cin, sout, 0, C)
+                ev = self._exchange(0, dev)
                 if ev is not None:
                     torch.cuda.current_stream(dev).wait_event(ev)
                 self._update(L, buf, cin, cout)
@@ -276,8 +357,8 @@ class PooledARWMH(ARWMH):
                 self._pending = None
             b = 0 if self._pending is None else 1 - self._pending[0]
             buf = self._bufs[b]
-            self._stats(L, cin, sout, buf, C)
-            ev = self._allreduce(buf, dev)  # in flight while the next block computes
+            self._stats(L, cin, sout, b, C)
+            ev = self._exchange(b, dev)  # in flight while the next block computes
             if self._pending is not None:
                 pb, pev = self._pending
                 if pev is not None:
@@ -349,7 +430,8 @@ class PooledARWMH(ARWMH):
         K = self.sync_every
         if int(n_steps) % K != 0:
             raise ValueError(f"n_steps ({n_steps}) must be a multiple of sync_every ({K})")
-        if self._world() == 1 and not self.overlap and not self.force_collective and not self._external():
+        if (self._world() == 1 and not self.overlap and not self.force_collective and not self._external()
+                and not self.exact_sums):
             L = _lib.lib()
             dev = state.z.device.index
             c = self._c(state)

@@ -372,6 +372,86 @@ int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_poole
  * its text in amh_last_error; nothing is retried. */
 int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm, void* stream);
 
+/* -------------------------------------------------------- exact sums ----
+ * The sums above are added in double, in an order that depends on how many
+ * chunks a rank holds, so two partitions of the same chains over ranks round
+ * differently.  The entries below replace everything between the chunk partial
+ * rows of the stats kernels (float32 values, each a function of its chunk's
+ * chains alone) and the update by integer arithmetic, which no partition can
+ * change (no counterpart in the reference, whose adaptation is
+ * per chain).  The format (csrc/amh_exact.h, compiled into the kernels and into
+ * the two host entries at the end):
+ *   - a component of the sums vector is AMH_EXACT_WORDS = AMH_EXACT_LIMBS + 1
+ *     int64 words.  Words 0 .. AMH_EXACT_LIMBS - 1 are signed limbs,
+ *       value = sum_j limb_j 2^(AMH_EXACT_BITS j - AMH_EXACT_FRAC);
+ *   - a finite float32 partial p with |p| < 2^80 adds the integer
+ *     trunc(p 2^AMH_EXACT_FRAC), cut into AMH_EXACT_BITS-bit pieces that carry
+ *     p's sign, to the limbs: no carry, no normalisation.  A partial whose
+ *     lowest set bit is at least 2^-AMH_EXACT_FRAC is represented exactly, bits
+ *     below that grid are cut toward zero (per partial, so the same for every
+ *     partition);
+ *   - a partial that is +-inf, NaN or has |p| >= 2^80 adds 1 to the last word
+ *     and nothing to the limbs.  A component whose last word is non-zero
+ *     converts to NaN, whatever its limbs hold; the other components are
+ *     untouched;
+ *   - only word-wise int64 addition ever happens to the words (within a rank,
+ *     over the steps of a block, in the all-reduce).  A piece is below
+ *     2^AMH_EXACT_BITS in magnitude, so AMH_EXACT_MAX_SUMMANDS partials per
+ *     component cannot overflow a word (8 ranks x 512 chunks x 16 steps =
+ *     65,536);
+ *   - the conversion rounds the exact rational value of the limb totals to the
+ *     nearest double (ties to even) through a wide integer.
+ * A run through these entries is byte-identical for every number of ranks whose
+ * shards start at multiples of amh_pooled_chunk_chains (a ragged tail only on
+ * the last rank); one rank goes the same way.  The exchanged message is
+ * amh_pooled_exact_size int64 words: 5 (d + d(d+1)/2 + 2) * 8 bytes, 86 KB at
+ * d = 64 and 1.3 MB at d = 256. */
+#define AMH_EXACT_BITS 40
+#define AMH_EXACT_LIMBS 4
+#define AMH_EXACT_FRAC 80
+#define AMH_EXACT_WORDS 5
+#define AMH_EXACT_MAX_SUMMANDS 8388608 /* 2^(63 - AMH_EXACT_BITS) */
+
+/* Number of int64 words of the exact sums, [V][AMH_EXACT_WORDS] with V =
+ * amh_pooled_sums_size (component-major). */
+int amh_pooled_exact_size(int32_t dim, int64_t* n);
+
+/* The chains per chunk of the pooled sums in a run of total_chains chains over
+ * all ranks: 16 * min(16, ceil(total_chains / 4096)) below d = 64, 128 above;
+ * at d = 64, where the Gaussian and a caller's potential run in 128-chain
+ * chunks and the other registry models in those of d < 64, the least common
+ * multiple of the two.  A rank's first global chain id must be a multiple. */
+int amh_pooled_chunk_chains(int32_t dim, int64_t total_chains, int64_t* n);
+
+/* amh_pooled_stats_k with the sums left as exact words: acc (device,
+ * amh_pooled_exact_size int64) is overwritten with this rank's words of the
+ * block.  total_chains >= num_chains is the chain count of all ranks; it cuts
+ * the chunks below d = 64 (amh_pooled_stats_k cuts them by num_chains), so a
+ * rank's chunks are those of the one-rank run.  Per chain the same bits as
+ * amh_pooled_stats_k (given the same chunks). */
+int amh_pooled_stats_k_exact(amh_handle* h, int64_t num_chains, int64_t total_chains, const amh_pooled_state* in,
+                             int32_t k_steps, float* z_out, float* pe_out, int64_t* acc, void* stream);
+
+/* amh_pooled_stats_external likewise; accumulate != 0: acc += the step's words
+ * (the K rounds of a block, in any order). */
+int amh_pooled_stats_external_exact(amh_handle* h, int64_t num_chains, int64_t total_chains,
+                                    const amh_pooled_state* in, int32_t t, const float* zprop, const float* pe_prop,
+                                    float* z_out, float* pe_out, int64_t* acc, int32_t accumulate, void* stream);
+
+/* The (all-reduced) words -> the V doubles amh_pooled_update_k consumes. */
+int amh_pooled_exact_to_sums(amh_handle* h, const int64_t* acc, double* sums, void* stream);
+
+/* amh_pooled_allreduce for the exact words: ncclAllReduce(sum, ncclInt64) of
+ * the n int64 at `acc`, RCCL resolved and errors reported the same way. */
+int amh_pooled_allreduce_i64(amh_handle* h, int64_t* acc, int64_t n, void* rccl_comm, void* stream);
+
+/* The format on the host (no handle, no device; host memory): the float32
+ * partial rows partials[rows][v] into acc[v][AMH_EXACT_WORDS] (accumulate != 0:
+ * added to what is there), and the words to out[v] doubles.  The same header
+ * functions the kernels compile. */
+int amh_pooled_exact_quantise(const float* partials, int64_t rows, int64_t v, int64_t* acc, int32_t accumulate);
+int amh_pooled_exact_to_double(const int64_t* acc, int64_t v, double* out);
+
 #ifdef __cplusplus
 }
 #endif
