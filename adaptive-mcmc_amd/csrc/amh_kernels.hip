@@ -40,15 +40,14 @@ __host__ __device__ __forceinline__ int wbuf_floats(int cpw, int d) {
 
 // Issue the DMA of one work item's chain state (global -> this wave's LDS
 // buffer).  Out-of-range bytes (past C) read as zero.
+template <int G, bool EXT>
+__device__ __forceinline__ void prefetch_item_small(const StepParams& p, int64_t first, int d, float* wb, int lane);
 template <int G, bool EXT, int AUX = kLoadAux>  // AUX: cache policy of the factor's DMA loads
 __device__ __forceinline__ void prefetch_item(const StepParams& p, int64_t first, int d, float* wb, int lane) {
   constexpr int CPW = Geo<G>::CPW;
   const uint32_t P = (uint32_t)(d * (d + 1) / 2);
   const int64_t nvalid = (p.C - first) < CPW ? (p.C - first) : CPW;  // chains of this item in range
   float* wL = wb;
-  float* wz = wb + wbuf_L(CPW, d);
-  float* wm = wz + wbuf_zd(CPW, d);
-  float* ws = wm + wbuf_zd(CPW, d);
   {
     const uint32_t bytes = (uint32_t)nvalid * P * 4u;
     const Buf b(uniform_ptr(p.in.scale + first * P), bytes);
@@ -64,6 +63,16 @@ __device__ __forceinline__ void prefetch_item(const StepParams& p, int64_t first
         __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rs, to_lds(wL + o / 4u), 4, (int)(o + 4u * lane), 0, 0, AUX);
     }
   }
+  prefetch_item_small<G, EXT>(p, first, d, wb, lane);
+}
+// ... everything but the factor: z, loc, the scalars and the key words
+template <int G, bool EXT>
+__device__ __forceinline__ void prefetch_item_small(const StepParams& p, int64_t first, int d, float* wb, int lane) {
+  constexpr int CPW = Geo<G>::CPW;
+  const int64_t nvalid = (p.C - first) < CPW ? (p.C - first) : CPW;
+  float* wz = wb + wbuf_L(CPW, d);
+  float* wm = wz + wbuf_zd(CPW, d);
+  float* ws = wm + wbuf_zd(CPW, d);
   {
     const uint32_t bytes = (uint32_t)(nvalid * d) * 4u;
     const uint32_t total = (uint32_t)(CPW * d) * 4u;
@@ -130,6 +139,17 @@ hipError_t diag_stamps_copy(void* host, size_t bytes) {
     st_prev = t_;                                             \
   }
 #define AMH_STAMP_COUNT(k) st_acc[k] += 1;
+// d = 64 step kernel (tools/s64_phases.py): per-wave totals of the loop's four
+// phases on the constant 100 MHz clock, kept in a second record per wave
+// (row kStampWaves / 2 + wave, slot 7 = 2) beside the start / end record
+#define AMH_S64_PHASE_INIT unsigned long long st_ph[4] = {0, 0, 0, 0}, st_pt = 0;
+#define AMH_S64_PHASE_MARK st_pt = __builtin_amdgcn_s_memrealtime();
+#define AMH_S64_PHASE(k)                                             \
+  {                                                                  \
+    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();  \
+    st_ph[k] += t_ - st_pt;                                          \
+    st_pt = t_;                                                      \
+  }
 #define AMH_STAMP_FLUSH(w)                                                                         \
   {                                                                                                \
     st_acc[7] = __builtin_amdgcn_s_memtime() - st_t0;                                              \
@@ -142,6 +162,9 @@ hipError_t diag_stamps_copy(void* host, size_t bytes) {
 #define AMH_STAMP(k)
 #define AMH_STAMP_COUNT(k)
 #define AMH_STAMP_FLUSH(w)
+#define AMH_S64_PHASE_INIT
+#define AMH_S64_PHASE_MARK
+#define AMH_S64_PHASE(k)
 #endif
 
 // -------------------------------------------------------------- step kernel --
@@ -867,6 +890,36 @@ constexpr size_t s64_lds_bytes() { return ((size_t)kS64Model + (size_t)WPB * kS6
 
 constexpr int s64_col(int j) { return j * 64 - j * (j - 1) / 2; }  // packed column offset
 
+// The factor moves between the wave buffer and HBM in kS64Pieces pieces: eight
+// of 256 floats (1 KB: 16 B per lane) and the 32-float tail.  The swap walks
+// the columns in 16 groups of four; after group g every float below
+// s64_col(4 g + 4) holds the outgoing chain's L' and the incoming chain's are
+// in registers, so a piece that ends at or below it can leave and be refilled.
+constexpr int kS64Pieces = 9;
+constexpr int s64_piece_end(int m) { return m < kS64Pieces - 1 ? 256 * (m + 1) : kS64P; }
+constexpr int s64_piece_group(int m) {  // the swap group after which piece m is finished
+  for (int g = 0; g < 16; ++g)
+    if (s64_col(4 * g + 4) >= s64_piece_end(m)) return g;
+  return -1;
+}
+constexpr int s64_piece_after(int g) {  // the piece that swap group g finishes, or -1
+  for (int m = 0; m < kS64Pieces; ++m)
+    if (s64_piece_group(m) == g) return m;
+  return -1;
+}
+constexpr bool s64_pieces_ok() {
+  int n = 0;
+  for (int g = 0; g < 16; ++g) n += s64_piece_after(g) >= 0;
+  for (int m = 0; m + 1 < kS64Pieces; ++m)
+    if (s64_piece_group(m) < 0 || s64_piece_group(m) >= s64_piece_group(m + 1)) return false;
+  return n == kS64Pieces;  // no group finishes two pieces
+}
+static_assert(256 * (kS64Pieces - 1) <= kS64P && kS64P - 256 * (kS64Pieces - 1) <= 64, "eight 1-KB pieces and a one-DMA tail");
+static_assert(s64_col(64) == kS64P && s64_pieces_ok(), "every piece is finished by its own swap group, in order");
+static_assert(s64_piece_group(0) == 1 && s64_piece_group(4) == 6 && s64_piece_group(7) == 14 &&
+                  s64_piece_group(kS64Pieces - 1) == 15,
+              "the table of DESIGN.md 3.1");
+
 // lanes r > J read the dword at a + OFF into x (others keep x); pending until lds_wait
 template <int J, int OFF>
 __device__ __forceinline__ void s64_rd_above(float& x, uint32_t a) {
@@ -1242,6 +1295,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   const unsigned long long st_start = __builtin_amdgcn_s_memrealtime();
   int st_items = 0;
 #endif
+  AMH_S64_PHASE_INIT
 
   const int64_t C = p.C;
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
@@ -1363,7 +1417,9 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     const int r = lane;
     const uint32_t la = wb_a + (uint32_t)r * 4u;  // this lane's dword in the factor region
 
+    AMH_S64_PHASE_MARK
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): item k has landed
+    AMH_S64_PHASE(0)  // (a) the wait for item k
     // the hand-over phase (stores, LDS -> registers, the next DMA) at high
     // wave priority so the memory queue is re-armed before other waves'
     // compute: 239 -> 236 us per launch (tools/gpu_prio.sh A/B)
@@ -1402,34 +1458,120 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     }
 
     // ---- swap: read item k's column j (lanes > j), write item k-1's column j
-    //      of L' = U diag(dl) (lanes >= j) at the same addresses, normalise
+    //      of L' = U diag(dl) (lanes >= j) at the same addresses, normalise.
+    //      The factor streams out and in while the swap runs: as soon as a
+    //      group has finished a piece (s64_piece_after), the piece's 16 B per
+    //      lane are read with the next group's [dl | 1/l] quarter-vectors (one
+    //      LDS round trip), stored to item k-1 in HBM, and the DMA of the same
+    //      piece of item k+1 is issued into the addresses just read.  The wait
+    //      at the top of the loop stays the only one on vector memory: every
+    //      LDS access from here to there is inline asm.
+    const bool have_nxt = ix(nxt) < kEnd;
+    const Buf Lnx(uniform_ptr(p.in.scale + ix(nxt) * P), P * 4u);  // (unused without a next item)
+    auto piece_in = [&](auto M) {  // DMA of piece M of item k+1, at its class's load policy
+      constexpr int m = M;
+      if (!have_nxt) return;
+      auto dma = [&](auto AUX) {
+        if constexpr (m < kS64Pieces - 1) {
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, to_lds(wb + 256 * m), 16, (int)(16u * lane), 1024 * m, 0,
+                                                   (int)AUX);
+        } else {
+          if (256 * m + lane < kS64P)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, to_lds(wb + 256 * m), 4, (int)(4u * lane), 1024 * m, 0,
+                                                     (int)AUX);
+        }
+      };
+      using std::integral_constant;
+      if constexpr (kS64LoadAuxHot == kS64LoadAuxCold) {
+        dma(integral_constant<int, kS64LoadAuxCold>{});
+      } else {
+        if ((nxt >> kS64TagShift) & kS64Hot) dma(integral_constant<int, kS64LoadAuxHot>{});
+        else dma(integral_constant<int, kS64LoadAuxCold>{});
+      }
+    };
+    const Buf Lout(uniform_ptr(p.out.scale + ix(wr ? prev : item) * P), P * 4u);  // (unused unless wr)
+    const int cls = (int)(prev >> kS64TagShift);
+    const uint32_t la16 = wb_a + (uint32_t)lane * 16u;
+    auto piece_out = [&](auto M, const f32x4& v) {  // piece M of L' -> item k-1, at its class's store policy
+      constexpr int m = M;
+      auto st = [&](auto AUX) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint32x4_t_, v), Lout.rs,
+                                               (int)(16u * (uint32_t)lane), 1024 * m, (int)AUX);
+      };
+      using std::integral_constant;
+      if constexpr (kS64StoreAuxHot == kS64StoreAuxMid && kS64StoreAuxTail == kS64StoreAuxMid) {
+        st(integral_constant<int, kS64StoreAuxMid>{});
+      } else {
+        if (cls & (int)kS64Hot) st(integral_constant<int, kS64StoreAuxHot>{});
+        else if (cls & (int)kS64Tail) st(integral_constant<int, kS64StoreAuxTail>{});
+        else st(integral_constant<int, kS64StoreAuxMid>{});
+      }
+    };
+    // One LDS round trip per group: the group's [dl | 1/l] quarter-vectors,
+    // the piece the previous group finished and the group's four columns are
+    // read together; L' columns are written after the wait and need none.
+    // `wr` (is there an L' to write) guards one block per group; without it
+    // (the first item, or a factor no step updated, copied verbatim above)
+    // the columns are only read and the whole factor's DMA follows the swap.
     static_for<16>([&](auto G4) {
       constexpr int g = G4;
+      constexpr int mp = g > 0 ? s64_piece_after(g - 1) : -1;  // the piece the previous group finished
       f32x4 dl4 = lds_ld4<16 * g>(zm_a);
       f32x4 in4 = lds_ld4<256 + 16 * g>(zm_a);
-      s64_tie(dl4, in4);
+      f32x4 pv;
+      if constexpr (mp >= 0) pv = lds_ld4<1024 * mp>(la16);
       float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       static_for<4>([&](auto Q) {
         constexpr int j = 4 * g + Q;
-        constexpr int off = (s64_col(j) - j) * 4;
-        if constexpr (j < D - 1) s64_rd_above<j, off>(t[(int)Q], la);
-        if (wr) s64_wr_from<j, off>(la, U[j] * dl4[(int)Q]);
+        if constexpr (j < D - 1) s64_rd_above<j, (s64_col(j) - j) * 4>(t[(int)Q], la);
       });
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+      if constexpr (mp >= 0) {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(dl4), "+v"(in4), "+v"(pv), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dl4), "+v"(in4), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+      }
+      if (wr) {
+        if constexpr (mp >= 0) {
+          piece_out(std::integral_constant<int, mp>{}, pv);
+          piece_in(std::integral_constant<int, mp>{});
+          if constexpr (mp == 0) {
+            AMH_S64_PHASE(1)  // (b) hand-over start -> first factor store
+          }
+        }
+        static_for<4>([&](auto Q) {
+          constexpr int j = 4 * g + Q;
+          s64_wr_from<j, (s64_col(j) - j) * 4>(la, U[j] * dl4[(int)Q]);
+        });
+      }
       static_for<4>([&](auto Q) {
         constexpr int j = 4 * g + Q;
         if constexpr (j < D - 1) s64_mul_above<j>(U[j], t[(int)Q], in4[(int)Q]);
       });
     });
-    if (wr) flush_factor(prev);
+    if (wr) {
+      constexpr int mp = s64_piece_after(15);  // the tail: 16 B of lanes 0 .. 7 (the store is clipped at P)
+      static_assert(mp == kS64Pieces - 1, "the last group finishes the tail");
+      f32x4 pv = lds_ld4<1024 * mp>(la16);
+      s64_tie(pv);
+      piece_out(std::integral_constant<int, mp>{}, pv);
+      piece_in(std::integral_constant<int, mp>{});
+    } else {
+      AMH_S64_PHASE(1)
+      s64_wait();
+      static_for<kS64Pieces>([&](auto M) { piece_in(M); });
+    }
 
+    // ---- z / loc / scalars of item k+1 (their region carried the swap's
+    //      vectors until the last group) and the ticket after it
     s64_wait();  // every LDS read of the buffer is done before the DMA refills it
     int64_t nxt2 = kEnd;
-    if (ix(nxt) < kEnd) {
-      prefetch(nxt, lane);
+    if (have_nxt) {
+      prefetch_item_small<64, false>(p, ix(nxt), D, wb, lane);
       nxt2 = ticket();
     }
     __builtin_amdgcn_s_setprio(0);
+    AMH_S64_PHASE(2)  // (c) -> last DMA issued
 
     nacc = 0;
     bool updated = false;
@@ -1590,6 +1732,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     prev_upd = Gp::any(updated);
     item = nxt;
     nxt = nxt2;
+    AMH_S64_PHASE(3)  // (d) compute
 #ifdef AMH_STAMPS
     ++st_items;
 #endif
@@ -1626,6 +1769,12 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       g_stamps[w * kStampSlots + 2] = (unsigned long long)st_items;
       g_stamps[w * kStampSlots + 3] = (unsigned long long)blockIdx.x;
       g_stamps[w * kStampSlots + 7] = 1;
+      if (w < kStampWaves / 2) {
+        const int64_t w2 = kStampWaves / 2 + w;
+        for (int k_ = 0; k_ < 4; ++k_) g_stamps[w2 * kStampSlots + k_] = st_ph[k_];
+        g_stamps[w2 * kStampSlots + 4] = (unsigned long long)st_items;
+        g_stamps[w2 * kStampSlots + 7] = 2;
+      }
     }
   }
 #endif
