@@ -233,3 +233,157 @@ def edge_init(kind, d, C, orc, seed=0, start="uniform"):
     from kernels_amd import PRNGKey
     ost = orc.init(om, PRNGKey(seed), C, init_z=z0)
     return kw, mk, om, ost, z0
+
+
+# ------------------------------------------- pooled mode, float64 reference --
+POOLED_LEAVES = ("i", "macc", "mu", "L", "lam", "asc", "cov")
+
+
+def pooled_ref_model(kind, om):
+    """The float64 potential and its float32 forward bound (oracle/pooled_np.py)
+    of an orc.Model."""
+    import pooled_np as pnp
+    if kind == "gaussian":
+        return pnp.gaussian_model(om.data, om.d)
+    if kind == "eight_schools":
+        return pnp.eight_schools_model(om.data, om.d)
+    raise ValueError(kind)
+
+
+def pooled_warm_start(kind, d, C, seed, K=1):
+    """-> (z0 float32 [C, d], shared): a pooled state in the typical set, so
+    that a block accepts a fair share of its proposals at every d (from the
+    uniform(-2, 2) start with the identity factor almost none are accepted at
+    large d).  shared has the leaves of orc.pooled_init_shared:
+    i, macc, mu, L, lam, asc, cov.
+
+    gaussian: z0 ~ N(m, P^-1), L = chol(P^-1) in float32, cov = P^-1 packed in
+    float64, lam = log(2.38 / sqrt(d)) (the optimal random-walk scale), mu = m
+    + 0.05, macc = 0.2, i = 20 K.  eight_schools: the oracle's own shared
+    state and z after 300 pooled CPU steps from uniform(-2, 2)."""
+    import orc
+    import pooled_np as pnp
+    from kernels_amd import PRNGKey
+    _, _, om = make_case(kind, d)
+    d = om.d
+    rng = np.random.default_rng(seed)
+    if kind == "gaussian":
+        ref = pooled_ref_model(kind, om)
+        cov = np.linalg.inv(ref.P)
+        cov = 0.5 * (cov + cov.T)
+        Lc = np.linalg.cholesky(cov)
+        z0 = (ref.m + rng.normal(size=(C, d)) @ Lc.T).astype(np.float32)
+        sh = dict(i=np.array([20 * K], np.int32), macc=np.array([0.2], np.float32),
+                  mu=(ref.m + 0.05).astype(np.float32), L=pnp.pack(Lc).astype(np.float32),
+                  lam=np.array([np.log(2.38 / np.sqrt(d))], np.float32), asc=np.zeros(1, np.float32),
+                  cov=pnp.pack(cov).astype(np.float64))
+        return z0, sh
+    if kind == "eight_schools":
+        z0 = rng.uniform(-2, 2, size=(C, d)).astype(np.float32)
+        st = orc.init(om, PRNGKey(seed), C, init_z=z0)
+        z, pe, keys = st.z, st.potential_energy, st.rng_key
+        sh = orc.pooled_init_shared(d)
+        for _ in range(300):
+            z, pe, sums = orc.pooled_stats(om, int(sh["i"][0]), z, pe, keys, sh["mu"], sh["L"], float(sh["lam"][0]))
+            orc.pooled_update(om, sums, sh)
+        return z.copy(), {k: np.array(v) for k, v in sh.items()}
+    raise ValueError(kind)
+
+
+def pooled_leaves(state):
+    """The shared leaves of a PooledState by their orc names."""
+    return dict(i=state.i, macc=state.mean_accept_prob, mu=state.adapt_state.loc, L=state.adapt_state.scale,
+                lam=state.adapt_state.log_step_size, asc=state.as_change, cov=state.cov)
+
+
+def apply_shared(state, sh):
+    """Copy a shared dict into the leaves of a PooledState, in place (the same
+    bits on both sides of a comparison).  Returns the state."""
+    import torch
+    for name, t in pooled_leaves(state).items():
+        t.copy_(torch.as_tensor(np.asarray(sh[name])).to(t.dtype))  # (same dtype on both sides: no rounding)
+    return state
+
+
+def shared_to_host(state):
+    return {k: v.detach().cpu().numpy().copy() for k, v in pooled_leaves(state).items()}
+
+
+def pooled_reference_shares(model, keys, z0, sh, K, W, blocks, lr_decay=2 / 3):
+    """The float64 reference alone, `blocks` blocks from the warm start: the
+    share of chain-steps that moved in each block."""
+    import pooled_np as pnp
+    cur = {k: np.array(v, np.float64 if k != "i" else np.int64) for k, v in sh.items()}
+    z, pe, out = np.asarray(z0, np.float64), None, []
+    for _ in range(blocks):
+        s = pnp.stats(model.U, int(cur["i"][0]), z, pe, keys, cur["mu"], cur["L"], float(cur["lam"][0]), K=K)
+        out.append(pnp.accepted_share(s))
+        up = pnp.update(pnp.pack_sums(s.S_d, s.S_dd, s.S_a, s.N), cur, K=K, num_warmup=W, lr_decay=lr_decay)
+        z, pe = s.z, s.pe
+        cur = dict(i=np.array([up.i]), macc=np.array([up.macc]), mu=up.mu, L=pnp.pack(up.L), lam=np.array([up.lam]),
+                   asc=np.array([up.asc]), cov=pnp.pack(up.cov))
+    return out
+
+
+class OraclePooled:
+    """The C oracle behind the interface pooled_f64_blocks drives."""
+
+    def __init__(self, orc, kind, d, C, K, W, seed, z0, sh):
+        from kernels_amd import PRNGKey
+        self.orc, self.K, self.W = orc, K, W
+        _, _, self.om = make_case(kind, d)
+        st = orc.init(self.om, PRNGKey(seed), C, init_z=z0)
+        self.z, self.pe, self.keys = st.z, st.potential_energy, st.rng_key
+        self.sh = {k: np.array(v) for k, v in sh.items()}
+
+    def shared(self):
+        return {k: np.array(v) for k, v in self.sh.items()}
+
+    def history(self):
+        """z after each of the K frozen single steps of the next block."""
+        z, pe, sh, out = self.z, self.pe, self.sh, []
+        for t in range(self.K):
+            z, pe, _ = self.orc.pooled_stats(self.om, int(sh["i"][0]) + t, z, pe, self.keys, sh["mu"], sh["L"],
+                                             float(sh["lam"][0]))
+            out.append(z)
+        return out, pe
+
+    def block(self):
+        sh = self.sh
+        z, pe, sums = self.orc.pooled_stats(self.om, int(sh["i"][0]), self.z, self.pe, self.keys, sh["mu"], sh["L"],
+                                            float(sh["lam"][0]), k_steps=self.K)
+        self.orc.pooled_update(self.om, sums, sh, num_warmup=self.W, k_steps=self.K)
+        self.z, self.pe = z, pe
+        return z, pe, sums
+
+
+def pooled_f64_blocks(impl, model, keys, K, W, blocks=3):
+    """Drive `impl` (OraclePooled, or the GPU twin of tests/test_gpu_pooled_f64.py)
+    for `blocks` blocks and compare each with the float64 restatement
+    (pooled_np.check_block).  K > 1: the block's intermediate z is not
+    observable, so the K frozen steps are first run one by one; the block's z
+    and pe must equal the last of them byte for byte, and its sums are bounded
+    against the float64 sums of that history.  Returns the per-block results
+    {quantity: error / bound}."""
+    import pooled_np as pnp
+    res = []
+    for b in range(blocks):
+        before = impl.shared()
+        z_in = np.array(impl.z_host() if hasattr(impl, "z_host") else impl.z)
+        hist = impl.history() if K > 1 else None
+        z, pe, sums = impl.block()
+        z, pe, sums = np.asarray(z), np.asarray(pe), np.asarray(sums)
+        if hist is not None:
+            zs, pe_last = hist
+            assert zs[-1].tobytes() == z.tobytes(), f"block {b + 1}: z is not that of {K} single steps"
+            assert np.asarray(pe_last).tobytes() == pe.tobytes(), f"block {b + 1}: pe is not that of {K} single steps"
+            zs = np.stack([z_in] + [np.asarray(x) for x in zs])
+        else:
+            zs = np.stack([z_in, z])
+        r = pnp.check_block(model, keys, before, zs, pe, sums, impl.shared(), K=K, num_warmup=W)
+        print(f"block {b + 1}: " + " ".join(f"{k}={v:.3g}" for k, v in r.items()))
+        C = z.shape[0]
+        assert r["skipped"] <= max(2, C / 100), (b, r["skipped"])
+        assert not pnp.worst(r), (f"block {b + 1}", pnp.worst(r))
+        res.append(r)
+    return res

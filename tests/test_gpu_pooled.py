@@ -5,24 +5,40 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_case
+from helpers import apply_shared, make_case, pooled_warm_start
 
 pytestmark = pytest.mark.gpu
 
 
-def _run(kind, d, C, steps, gpu, orc, seed=0, K=1):
+def _run(kind, d, C, steps, gpu, orc, seed=0, K=1, warm=False):
+    """warm: start both sides from helpers.pooled_warm_start (the typical set,
+    where a fair share of the proposals is accepted at every d) and assert the
+    oracle's moved share of every block's chain-steps."""
     from kernels_amd import PooledARWMH, PRNGKey
     kw, mk, om = make_case(kind, d)
     k = PooledARWMH(num_chains=C, sync_every=K, **kw)
     z0 = np.random.default_rng(seed).uniform(-2, 2, size=(C, om.d)).astype(np.float32)
+    if warm:
+        z0, warm_sh = pooled_warm_start(kind, d, C, seed, K)
     st = k.init(PRNGKey(seed), 0, torch.as_tensor(z0), (), mk)
     ost = orc.init(om, PRNGKey(seed), C, init_z=z0)
     z, pe, keys = ost.z, ost.potential_energy, ost.rng_key
     assert np.array_equal(st.rng_key.cpu().numpy().view(np.uint32), keys)
     assert np.array_equal(st.potential_energy.cpu().numpy().view(np.uint32), pe.view(np.uint32))
     sh = orc.pooled_init_shared(om.d)
+    if warm:
+        sh = {f: np.array(v) for f, v in warm_sh.items()}
+        apply_shared(st, sh)
     for t in range(steps):
         st = k.sample(st)
+        if warm:  # the block's K frozen steps one by one: chain-steps that moved
+            zt, pt, moved = z, pe, 0
+            for s in range(K):
+                zn, pt, _ = orc.pooled_stats(om, int(sh["i"][0]) + s, zt, pt, keys, sh["mu"], sh["L"],
+                                             float(sh["lam"][0]))
+                moved += int(np.any(zn != zt, axis=1).sum())
+                zt = zn
+            assert 0.10 <= moved / (K * C) <= 0.50, f"{kind} d={d}: moved share {moved / (K * C):.3f} in block {t + 1}"
         z, pe, sums = orc.pooled_stats(om, int(sh["i"][0]), z, pe, keys, sh["mu"], sh["L"], float(sh["lam"][0]),
                                        k_steps=K)
         torch.cuda.synchronize()
@@ -52,6 +68,19 @@ def _run(kind, d, C, steps, gpu, orc, seed=0, K=1):
                                             ("gaussian", 224, 300, 3)])
 def test_pooled_bitexact(kind, d, C, steps, gpu, orc):
     _run(kind, d, C, steps, gpu, orc)
+
+
+@pytest.mark.parametrize("d,C,K", [(64, 300, 1), (96, 257, 1), (128, 300, 1), (128, 300, 2), (160, 260, 1),
+                                   (224, 280, 1), (256, 257, 1), (256, 257, 2)])
+def test_pooled_warm_bitexact(d, C, K, gpu, orc):
+    """The accept path of the MFMA kernels.  From uniform(-2, 2) with the
+    identity factor the cases above accept almost nothing at large d (0 to 3
+    of 600 chains per step at d = 256 and 160), so the writes of z' and pe'
+    and a moved chain's delta were compared with nothing.  Here both sides
+    start from the same warm shared state in the typical set: every block
+    moves 10 % to 50 % of its chain-steps, and sums, shared state and chain
+    state agree byte for byte over 3 blocks."""
+    _run("gaussian", d, C, 3, gpu, orc, seed=7, K=K, warm=True)
 
 
 @pytest.mark.parametrize("d,C", [(16, 999), (128, 300), (256, 257), (64, 70000), (64, 4097)])

@@ -107,6 +107,46 @@ def test_pooled_external_bitexact(d, C, gpu, orc):
     assert 0 < accepted < 5 * C  # both branches of the accept ran
 
 
+def test_pooled_external_warm_bitexact(gpu, orc):
+    """d = 128 from a warm shared state in the typical set of this potential
+    (coordinates 0 and d - 1 at their target scales with the matching factor,
+    lambda = log(2.38 / sqrt(2)) for its two informative coordinates): every
+    step moves 10 % to 50 % of the chains, and the sums, the shared state and
+    the chain state agree with the oracle byte for byte over 3 steps."""
+    from helpers import apply_shared
+    from kernels_amd import PooledARWMH, PRNGKey
+    d, C = 128, 300
+    om, sh = _orc_model(orc, d), orc.pooled_init_shared(d)
+    k = PooledARWMH(potential_fn=_torch_U(d), num_chains=C)
+    var = np.ones(d)
+    var[0], var[d - 1] = 0.5, 2.0
+    z0 = _z0(C, d, 7)
+    z0[:, 0] = (np.random.default_rng(70).normal(size=C) * np.sqrt(var[0])).astype(np.float32)
+    z0[:, d - 1] = (np.random.default_rng(71).normal(size=C) * np.sqrt(var[d - 1])).astype(np.float32)
+    diag = np.cumsum([0] + [d - j for j in range(d - 1)])  # packed offsets of the diagonal
+    sh["i"][:] = 20
+    sh["macc"][:] = 0.2
+    sh["mu"][:] = 0.05
+    sh["lam"][:] = np.log(2.38 / np.sqrt(2.0))
+    sh["L"][diag] = np.sqrt(var).astype(np.float32)
+    sh["cov"][diag] = var
+    st = apply_shared(k.init(PRNGKey(7), 0, torch.as_tensor(z0), (), {}), sh)
+    ost = orc.init(om, PRNGKey(7), C, init_z=z0)
+    z, pe, keys = ost.z, ost.potential_energy, ost.rng_key
+    assert np.array_equal(st.potential_energy.cpu().numpy().view(np.uint32), pe.view(np.uint32))
+    for t in range(3):
+        st = k.sample(st)
+        zn, pe, sums = orc.pooled_stats(om, int(sh["i"][0]), z, pe, keys, sh["mu"], sh["L"], float(sh["lam"][0]))
+        share = float(np.any(zn != z, axis=1).mean())
+        assert 0.10 <= share <= 0.50, f"moved share {share:.3f} at step {t + 1}"
+        z = zn
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(k._sums.cpu().numpy().view(np.uint64), sums.view(np.uint64),
+                                      err_msg=f"sums step {t + 1}")
+        orc.pooled_update(om, sums, sh)
+        _assert_state(st, z, pe, sh, f"warm d={d} step {t + 1}")
+
+
 @pytest.mark.parametrize("d,C,K", [(7, 517, 3), (64, 300, 4), (128, 333, 3)])
 def test_pooled_external_blocks(d, C, K, gpu, orc):
     """sync_every = K: a block is K rounds propose -> U -> accept, each
