@@ -920,26 +920,98 @@ static_assert(s64_piece_group(0) == 1 && s64_piece_group(4) == 6 && s64_piece_gr
                   s64_piece_group(kS64Pieces - 1) == 15,
               "the table of DESIGN.md 3.1");
 
-// lanes r > J read the dword at a + OFF into x (others keep x); pending until lds_wait
-template <int J, int OFF>
-__device__ __forceinline__ void s64_rd_above(float& x, uint32_t a) {
-  uint64_t sv;
-  asm volatile("s_mov_b64 %1, exec\n\ts_lshl_b64 exec, -1, %3\n\tds_read_b32 %0, %2 offset:%4\n\ts_mov_b64 exec, %1"
-               : "+v"(x), "=&s"(sv) : "v"(a), "n"(J + 1), "n"(OFF));
+// The swap's group of four columns j = 4 G .. 4 G + 3 as whole statements:
+// one s_lshl_b64 exec per mask and ONE exec restore per statement, where a
+// statement per masked operation saves, shifts and restores exec around it
+// and has hipcc's boundary pad after it (80 instructions per group).  exec is
+// restored with s_mov_b64 exec, -1 and not from a saved pair (no SGPR pair
+// live across the statement): valid only because every wave of the kernel is
+// full (the block is WPB whole waves, asserted in the kernel) and the swap
+// runs under wave-uniform control only.  None of the pairs inside a string
+// needs a wait state: SALU write of exec -> DS / VALU, VALU write of a VGPR
+// -> DS read of it as data.
+//
+// s64_group_read: [dl | 1/l] quarter-vectors of the group, the piece the
+// previous group finished (MP >= 0: 16 B per lane at la16), column j of the
+// incoming factor on lanes r > j, in that order, and their one wait.  t[k]
+// is written on lanes r > j only and is consumed under the same mask only.
+#define AMH_SWG_RD(k) "s_lshl_b64 exec, -1, %[m" #k "]\n\tds_read_b32 %[t" #k "], %[la] offset:%[o" #k "]\n\t"
+#define AMH_SWG_RD_HEAD "ds_read_b128 %[dl], %[zm] offset:%[od]\n\tds_read_b128 %[in], %[zm] offset:%[oi]\n\t"
+#define AMH_SWG_RD_PIECE "ds_read_b128 %[pv], %[lp] offset:%[op]\n\t"
+#define AMH_SWG_RD_TAIL "s_mov_b64 exec, -1\n\ts_waitcnt lgkmcnt(0)"
+template <int G, int MP>
+__device__ __forceinline__ void s64_group_read(f32x4& dl4, f32x4& in4, f32x4& pv, float (&t)[4], uint32_t zm_a,
+                                               uint32_t la16, uint32_t la) {
+  constexpr int j = 4 * G;
+  static_assert(G < 15 || MP >= 0, "the last group reads the piece that group 14 finished");
+#define AMH_SWG_RD_OPS3                                                                                       \
+  [zm] "v"(zm_a), [la] "v"(la), [od] "n"(16 * G), [oi] "n"(256 + 16 * G), [m0] "n"(j + 1), [m1] "n"(j + 2), \
+      [m2] "n"(j + 3), [o0] "n"((s64_col(j) - j) * 4), [o1] "n"((s64_col(j + 1) - (j + 1)) * 4),             \
+      [o2] "n"((s64_col(j + 2) - (j + 2)) * 4)
+  if constexpr (G == 15) {  // column 63 has nothing below its diagonal
+    asm volatile(AMH_SWG_RD_HEAD AMH_SWG_RD_PIECE AMH_SWG_RD(0) AMH_SWG_RD(1) AMH_SWG_RD(2) AMH_SWG_RD_TAIL
+                 : [dl] "=&v"(dl4), [in] "=&v"(in4), [pv] "=&v"(pv), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]),
+                   [t2] "=&v"(t[2])
+                 : AMH_SWG_RD_OPS3, [lp] "v"(la16), [op] "n"(1024 * MP));
+  } else if constexpr (MP >= 0) {
+    asm volatile(AMH_SWG_RD_HEAD AMH_SWG_RD_PIECE AMH_SWG_RD(0) AMH_SWG_RD(1) AMH_SWG_RD(2) AMH_SWG_RD(3)
+                     AMH_SWG_RD_TAIL
+                 : [dl] "=&v"(dl4), [in] "=&v"(in4), [pv] "=&v"(pv), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]),
+                   [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
+                 : AMH_SWG_RD_OPS3, [m3] "n"(j + 4), [o3] "n"((s64_col(j + 3) - (j + 3)) * 4), [lp] "v"(la16),
+                   [op] "n"(1024 * MP));
+  } else {
+    asm volatile(AMH_SWG_RD_HEAD AMH_SWG_RD(0) AMH_SWG_RD(1) AMH_SWG_RD(2) AMH_SWG_RD(3) AMH_SWG_RD_TAIL
+                 : [dl] "=&v"(dl4), [in] "=&v"(in4), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]),
+                   [t3] "=&v"(t[3])
+                 : AMH_SWG_RD_OPS3, [m3] "n"(j + 4), [o3] "n"((s64_col(j + 3) - (j + 3)) * 4));
+  }
+#undef AMH_SWG_RD_OPS3
 }
-// lanes r >= J write v to a + OFF
-template <int J, int OFF>
-__device__ __forceinline__ void s64_wr_from(uint32_t a, float v) {
-  uint64_t sv;
-  asm volatile("s_mov_b64 %0, exec\n\ts_lshl_b64 exec, -1, %3\n\tds_write_b32 %1, %2 offset:%4\n\ts_mov_b64 exec, %0"
-               : "=&s"(sv) : "v"(a), "v"(v), "n"(J), "n"(OFF) : "memory");
+// L' = U diag(dl) of the outgoing chain, columns j on lanes r >= j, into the
+// addresses just read (the products take dl's registers, on every lane)
+#define AMH_SWG_LP                                                                      \
+  "v_mul_f32 %[d0], %[u0], %[d0]\n\tv_mul_f32 %[d1], %[u1], %[d1]\n\t"                  \
+  "v_mul_f32 %[d2], %[u2], %[d2]\n\tv_mul_f32 %[d3], %[u3], %[d3]\n\t"
+#define AMH_SWG_WR(k) "ds_write_b32 %[la], %[d" #k "] offset:%[o" #k "]\n\t"
+#define AMH_SWG_NRM(k) "v_mul_f32 %[u" #k "], %[t" #k "], %[i" #k "]\n\t"
+#define AMH_SWG_SH(k) "s_lshl_b64 exec, -1, %[m" #k "]\n\t"
+#define AMH_SWG_OFFS                                                                                          \
+  [o0] "n"((s64_col(j) - j) * 4), [o1] "n"((s64_col(j + 1) - (j + 1)) * 4),                                   \
+      [o2] "n"((s64_col(j + 2) - (j + 2)) * 4), [o3] "n"((s64_col(j + 3) - (j + 3)) * 4), [m0] "n"(j),        \
+      [m1] "n"(j + 1), [m2] "n"(j + 2), [m3] "n"(j + 3)
+// the L' writes (also of the last item of a wave, where nothing comes in)
+template <int G>
+__device__ __forceinline__ void s64_group_write(const float (&U)[64], uint32_t la, const f32x4& dl4) {
+  constexpr int j = 4 * G;
+  float d0 = dl4[0], d1 = dl4[1], d2 = dl4[2], d3 = dl4[3];
+  asm volatile(AMH_SWG_LP AMH_SWG_SH(0) AMH_SWG_WR(0) AMH_SWG_SH(1) AMH_SWG_WR(1) AMH_SWG_SH(2) AMH_SWG_WR(2)
+                   AMH_SWG_SH(3) AMH_SWG_WR(3) "s_mov_b64 exec, -1"
+               : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3)
+               : [la] "v"(la), [u0] "v"(U[j]), [u1] "v"(U[j + 1]), [u2] "v"(U[j + 2]), [u3] "v"(U[j + 3]), AMH_SWG_OFFS
+               : "memory");
 }
-// lanes r > J: u = t * s
-template <int J>
-__device__ __forceinline__ void s64_mul_above(float& u, float t, float s) {
-  uint64_t sv;
-  asm volatile("s_mov_b64 %1, exec\n\ts_lshl_b64 exec, -1, %4\n\tv_mul_f32 %0, %2, %3\n\ts_mov_b64 exec, %1"
-               : "+v"(u), "=&s"(sv) : "v"(t), "v"(s), "n"(J + 1));
+// the normalisation U_rj = t_j / l_j of the incoming chain on lanes r > j.  (The
+// L' writes interleaved with it share masks, five shifts for eight operations,
+// but the swap writes only under `wr`: two statements that define U on the two
+// sides of a branch cost copies and, on this kernel, 51 spilled VGPRs.)
+template <int G>
+__device__ __forceinline__ void s64_group_norm(float (&U)[64], const f32x4& in4, const float (&t)[4]) {
+  constexpr int j = 4 * G;
+  if constexpr (G < 15) {
+    asm volatile(AMH_SWG_SH(1) AMH_SWG_NRM(0) AMH_SWG_SH(2) AMH_SWG_NRM(1) AMH_SWG_SH(3) AMH_SWG_NRM(2) AMH_SWG_SH(4)
+                     AMH_SWG_NRM(3) "s_mov_b64 exec, -1"
+                 : [u0] "+v"(U[j]), [u1] "+v"(U[j + 1]), [u2] "+v"(U[j + 2]), [u3] "+v"(U[j + 3])
+                 : [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]), [i0] "v"(in4[0]), [i1] "v"(in4[1]),
+                   [i2] "v"(in4[2]), [i3] "v"(in4[3]), [m1] "n"(j + 1), [m2] "n"(j + 2), [m3] "n"(j + 3),
+                   [m4] "n"(j + 4));
+  } else {
+    asm volatile(AMH_SWG_SH(1) AMH_SWG_NRM(0) AMH_SWG_SH(2) AMH_SWG_NRM(1) AMH_SWG_SH(3) AMH_SWG_NRM(2)
+                 "s_mov_b64 exec, -1"
+                 : [u0] "+v"(U[j]), [u1] "+v"(U[j + 1]), [u2] "+v"(U[j + 2])
+                 : [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [i0] "v"(in4[0]), [i1] "v"(in4[1]),
+                   [i2] "v"(in4[2]), [m1] "n"(j + 1), [m2] "n"(j + 2), [m3] "n"(j + 3));
+  }
 }
 // LDS batches read and waited for in ONE statement (outputs "=&v"): per
 // batch one boundary pad instead of two (separate read and wait statements
@@ -1262,8 +1334,11 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
 // the state is the same but for mean_accept_prob / log_step_size (absent).
 template <int WPB, bool kASSS = false>
 __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
+  const StepParams& p_outer = p;
   constexpr int D = 64;
   constexpr uint32_t P = kS64P;
+  // the swap's statements restore exec to all ones (s64_group_read): the block is whole waves
+  static_assert(WPB >= 1 && (WPB * 64) % 64 == 0, "d = 64 step kernel: every wave of the block is full");
   using Gp = Grp<64>;
   using M = GaussianM<64>;
   extern __shared__ float lds[];
@@ -1345,6 +1420,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 
   // z, loc and the scalars of chain `c` from registers
   auto store_small = [&](int64_t c, int r) {
+    const StepParams& p = reload_kernarg(p_outer);
     p.out.z[c * D + r] = z;
     p.out.loc[c * D + r] = mu;
     if (r == 0) {
@@ -1471,14 +1547,19 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     auto piece_in = [&](auto M) {  // DMA of piece M of item k+1, at its class's load policy
       constexpr int m = M;
       if (!have_nxt) return;
+      // The piece's LDS address (M0) is one scalar add from the wave buffer's
+      // base, made opaque here: nine loop-invariant addresses would otherwise
+      // be kept across the loop, spilled to VGPR lanes and read back with
+      // v_readlane at every use.
+      uint32_t base = wb_a;
+      asm volatile("" : "+s"(base));
+      lds_void* dst = (lds_void*)(uintptr_t)(base + 1024u * m);
       auto dma = [&](auto AUX) {
         if constexpr (m < kS64Pieces - 1) {
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, to_lds(wb + 256 * m), 16, (int)(16u * lane), 1024 * m, 0,
-                                                   (int)AUX);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, dst, 16, (int)(16u * lane), 1024 * m, 0, (int)AUX);
         } else {
           if (256 * m + lane < kS64P)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, to_lds(wb + 256 * m), 4, (int)(4u * lane), 1024 * m, 0,
-                                                     (int)AUX);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(Lnx.rs, dst, 4, (int)(4u * lane), 1024 * m, 0, (int)AUX);
         }
       };
       using std::integral_constant;
@@ -1516,21 +1597,9 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     static_for<16>([&](auto G4) {
       constexpr int g = G4;
       constexpr int mp = g > 0 ? s64_piece_after(g - 1) : -1;  // the piece the previous group finished
-      f32x4 dl4 = lds_ld4<16 * g>(zm_a);
-      f32x4 in4 = lds_ld4<256 + 16 * g>(zm_a);
-      f32x4 pv;
-      if constexpr (mp >= 0) pv = lds_ld4<1024 * mp>(la16);
-      float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      static_for<4>([&](auto Q) {
-        constexpr int j = 4 * g + Q;
-        if constexpr (j < D - 1) s64_rd_above<j, (s64_col(j) - j) * 4>(t[(int)Q], la);
-      });
-      if constexpr (mp >= 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(dl4), "+v"(in4), "+v"(pv), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dl4), "+v"(in4), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-      }
+      f32x4 dl4, in4, pv;
+      float t[4];  // no initial value: lanes a column does not read are never consumed
+      s64_group_read<g, mp>(dl4, in4, pv, t, zm_a, la16, la);
       if (wr) {
         if constexpr (mp >= 0) {
           piece_out(std::integral_constant<int, mp>{}, pv);
@@ -1539,15 +1608,9 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
             AMH_S64_PHASE(1)  // (b) hand-over start -> first factor store
           }
         }
-        static_for<4>([&](auto Q) {
-          constexpr int j = 4 * g + Q;
-          s64_wr_from<j, (s64_col(j) - j) * 4>(la, U[j] * dl4[(int)Q]);
-        });
+        s64_group_write<g>(U, la, dl4);
       }
-      static_for<4>([&](auto Q) {
-        constexpr int j = 4 * g + Q;
-        if constexpr (j < D - 1) s64_mul_above<j>(U[j], t[(int)Q], in4[(int)Q]);
-      });
+      s64_group_norm<g>(U, in4, t);
     });
     if (wr) {
       constexpr int mp = s64_piece_after(15);  // the tail: 16 B of lanes 0 .. 7 (the store is clipped at P)
@@ -1748,10 +1811,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
         constexpr int g = G4;
         f32x4 dl4 = lds_ld4<16 * g>(x_a);
         s64_tie(dl4);
-        static_for<4>([&](auto Q) {
-          constexpr int j = 4 * g + Q;
-          s64_wr_from<j, (s64_col(j) - j) * 4>(la, U[j] * dl4[(int)Q]);
-        });
+        s64_group_write<g>(U, la, dl4);
       });
       flush_factor(prev);
     } else {
