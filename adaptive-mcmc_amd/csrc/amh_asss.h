@@ -1,6 +1,6 @@
 // amh_asss.h -- one ASSS transition (python/kernels/asss.py:197-251) of a
 // lane group's chain, shared by the ASSS kernels (amh_asss.hip) and the d = 64
-// persistent step kernel's ASSS instantiation (amh_kernels.hip).  Bit spec:
+// persistent step kernel's ASSS instantiation (amh_step64.hip).  Bit spec:
 // oracle/amh_oracle.c orc_asss_step.
 #pragma once
 #include "amh_device.h"

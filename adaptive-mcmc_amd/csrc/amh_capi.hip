@@ -1,6 +1,7 @@
 // amh_capi.hip -- the extern "C" boundary of libamh.so (include/amh.h).
 // Validates arguments, keeps per-handle configuration and model binding, and
-// enqueues the kernels of amh_kernels.hip on the caller's stream.
+// enqueues the kernels of amh_kernels.hip, amh_step64.hip and the other
+// csrc/*.hip files on the caller's stream.
 // Layout: the handle and its helpers, then one extern "C" region per family
 // (core, external potential, ASSS, evaluation, pooled covariance, diagnostics),
 // each preceded by the helpers only that family uses.
@@ -1338,6 +1339,10 @@ extern "C" {
 // diagnostic build only: copy the step kernel's per-wave phase stamps
 int amh_diag_stamps(void* host, int64_t bytes) {
   return amh::diag_stamps_copy(host, (size_t)bytes) == hipSuccess ? 0 : -1;
+}
+// the d = 64 step kernel's per-wave records (amh_step64.hip: 8 x u64 per wave)
+int amh_diag_s64_stamps(void* host, int64_t bytes) {
+  return amh::diag_s64_stamps_copy(host, (size_t)bytes) == hipSuccess ? 0 : -1;
 }
 // pooled large-d update kernel phase totals (8 x u64)
 int amh_diag_upd_stamps(void* host) { return amh::diag_upd_stamps_copy(host) == hipSuccess ? 0 : -1; }

@@ -1,4 +1,4 @@
-// amh_internal.h -- kernel parameter blocks shared by amh_kernels.hip and the
+// amh_internal.h -- kernel parameter blocks shared by the kernel files and the
 // C-ABI layer amh_capi.hip.  Not part of the public ABI (include/amh.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -249,7 +249,8 @@ hipError_t run_pooled_exact_reduce(const void* partials, bool f32_rows, int64_t 
                                    int64_t* acc, int accumulate, hipStream_t s);
 hipError_t run_pooled_exact_convert(const int64_t* acc, int64_t V, double* sums, hipStream_t s);
 hipError_t run_asss_step(int model_id, const StepParams& p, hipStream_t s);  // amh_asss.hip
-hipError_t run_asss_step64(const StepParams& p, hipStream_t s);  // amh_kernels.hip (d = 64 Gaussian)
+hipError_t run_asss_step64(const StepParams& p, hipStream_t s);  // amh_step64.hip (d = 64 Gaussian)
+hipError_t run_step64(const StepParams& p, hipStream_t s);       // amh_step64.hip (ARWMH, d = 64 Gaussian: run_step)
 hipError_t run_asss_pnx(int model_id, const AsssPnxParams& p, hipStream_t s);
 // evaluation metrics (amh_eval.hip)
 int64_t kernel_sum_blocks(int64_t n, int64_t m);
@@ -325,6 +326,7 @@ hipError_t run_chain_keys(uint32_t k0, uint32_t k1, int64_t offset, int64_t n, u
                           hipStream_t s);
 #ifdef AMH_STAMPS
 hipError_t diag_stamps_copy(void* host, size_t bytes);
+hipError_t diag_s64_stamps_copy(void* host, size_t bytes);
 hipError_t diag_upd_stamps_copy(void* host);
 hipError_t diag_f64_stamps_copy(void* host);
 hipError_t diag_u64_timeline_copy(void* host);

@@ -1,5 +1,5 @@
 // amh_s64_sched.h -- the block-local schedule of arwmh_step64_kernel, stated
-// once for the kernel (amh_kernels.hip) and for the host (amh_capi.hip
+// once for the kernel (amh_step64.hip) and for the host (amh_capi.hip
 // amh_step64_schedule, tests/test_step64_schedule.py).
 //
 // A block owns n chains, local indices 0 ... n - 1, and its waves draw them
@@ -15,7 +15,7 @@
 //   mid   the rest.
 // h <= n / 2, so no chain is both hot and tail; h = 0 for n < 3, and then every
 // chain is mid.  The class picks the cache policy of
-// the chain's factor traffic (kS64LoadAux* / kS64StoreAux*, amh_kernels.hip);
+// the chain's factor traffic (kS64LoadAux* / kS64StoreAux*, amh_step64.hip);
 // it changes no result.
 #pragma once
 #include <hip/hip_runtime.h>

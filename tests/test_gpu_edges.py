@@ -5,7 +5,7 @@ against per-chain ifs, casts of out-of-range floats).  Scenarios and the
 NaN-aware comparison are in tests/helpers.py; tests/test_edges.py shows on the
 CPU that the scenarios reach the edges and that the oracle is right there.
 
-Read before the first run (amh_kernels.hip, amh_split.hip, amh_big.hip,
+Read before the first run (amh_kernels.hip, amh_step64.hip, amh_split.hip, amh_big.hip,
 amh_asss.h, amh_pooled.hip, amh_big_pooled.hip, amh_device.h, amh_math.h): no
 memory index, trip count or launch dimension derives from a float state value
 -- lookup_gamma indexes by the integer step number, the ASSS shrink loops end

@@ -24,7 +24,7 @@ import shutil
 import statistics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "arwmh_step64_kernel"  # the d = 64 specialisation (amh_kernels.hip)
+KERNEL = "arwmh_step64_kernel"  # the d = 64 specialisation (amh_step64.hip)
 
 
 def step_rows(path):

@@ -34,7 +34,7 @@ for _ in range(300):
 torch.cuda.synchronize()
 W, S = 1 << 16, 8
 L = _lib.lib()
-L.amh_diag_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+L.amh_diag_s64_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
 print(f"library {os.environ['AMH_LIB_PATH']}")
 NAMES = ["(a) wait", "(b) ->1st store", "(c) ->last DMA", "(d) compute"]
 for rep in range(3):
@@ -45,13 +45,13 @@ for rep in range(3):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
     buf = np.zeros(W * S, np.uint64)
-    assert L.amh_diag_stamps(buf.ctypes.data, buf.nbytes) == 0
+    assert L.amh_diag_s64_stamps(buf.ctypes.data, buf.nbytes) == 0
     s = buf.reshape(W, S)
-    ph = s[s[:, 7] == 2]
+    ph = s[s[:, 1] > 0]  # one record per wave (amh_step64.hip): start, end, items, block, phases (a) .. (d)
     if len(ph) == 0:
         sys.exit("no phase records: not a stamps build of this kernel")
-    items = ph[:, 4].astype(np.float64)
-    tot = ph[:, :4].astype(np.float64) * 10e-3  # us per wave
+    items = ph[:, 2].astype(np.float64)
+    tot = ph[:, 4:8].astype(np.float64) * 10e-3  # us per wave
     loop = tot.sum(axis=1)
     print(f"launch {ms * 1e3:.1f} us (events); waves {len(ph)}; items/wave {items.mean():.2f}; "
           f"loop time per wave {loop.mean():.1f} us (min {loop.min():.1f} max {loop.max():.1f})")

@@ -29,7 +29,7 @@ for _ in range(300):
 torch.cuda.synchronize()
 W, S = 1 << 16, 8
 L = _lib.lib()
-L.amh_diag_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+L.amh_diag_s64_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
 for rep in range(3):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -38,9 +38,9 @@ for rep in range(3):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
     buf = np.zeros(W * S, np.uint64)
-    assert L.amh_diag_stamps(buf.ctypes.data, buf.nbytes) == 0
+    assert L.amh_diag_s64_stamps(buf.ctypes.data, buf.nbytes) == 0
     s = buf.reshape(W, S)
-    s = s[s[:, 7] == 1]
+    s = s[s[:, 1] > 0]  # one record per wave (amh_step64.hip): start, end, items, block, four phase totals
     t0 = s[:, 0].min()
     start = (s[:, 0] - t0) * 10e-3  # us
     end = (s[:, 1] - t0) * 10e-3

@@ -1,7 +1,9 @@
 """Phase breakdown of the step kernel from the diagnostic build
 (make -C adaptive-mcmc_amd/csrc stamps): per-wave s_memtime totals of
 wait-for-DMA / store previous / LDS->registers / prefetch issue / compute /
-tail, averaged over waves, per item.  Usage (GPU box):
+tail, averaged over waves, per item.  The records are those of the general
+kernel (arwmh_step_kernel): the d = 64 Gaussian is sent to it too (AMH_STEP64=0;
+the d = 64 kernel has its own record, tools/s64_phases.py).  Usage (GPU box):
   python3 tools/stamps.py [--chains C] [--steps N]
 """
 import argparse
@@ -13,6 +15,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("AMH_LIB_PATH", os.path.join(ROOT, "adaptive-mcmc_amd", "lib", "diag", "libamh_stamps.so"))
+os.environ.setdefault("AMH_STEP64", "0")  # the general kernel at d = 64 as well
 sys.path.insert(0, os.path.join(ROOT, "adaptive-mcmc_amd"))
 
 import torch  # noqa: E402
