@@ -3,7 +3,7 @@
 // enqueues the kernels of amh_kernels.hip, amh_step64.hip and the other
 // csrc/*.hip files on the caller's stream.
 // Layout: the handle and its helpers, then one extern "C" region per family
-// (core, external potential, ASSS, evaluation, pooled covariance, diagnostics),
+// (core, external potential, ASSS, evaluation, pooled covariance, pooled ASSS, diagnostics),
 // each preceded by the helpers only that family uses.
 #include <hip/hip_runtime.h>
 
@@ -1326,6 +1326,111 @@ int amh_pooled_exact_to_double(const int64_t* acc, int64_t v, double* out) {
     int64_t w[amh::kExactWords];
     for (int j = 0; j < amh::kExactWords; ++j) w[j] = acc[c * amh::kExactWords + j];
     out[c] = amh::exact_to_double(w);
+  }
+  return AMH_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------- pooled ASSS --
+// The slice transition against the shared factor (amh_pooled_asss.hip) and
+// the ASSS form of the d <= 64 update; the sums, their reduction and the
+// exchange are the pooled mode's own.
+namespace {
+
+// the checks the three entries share, reported as `who`
+int pooled_asss_enter(amh_handle* h, const char* who) {
+  if (int rc = enter(h, who, true)) return rc;
+  if (h->model_id == AMH_MODEL_EXTERNAL)
+    return fail(h, AMH_EINVAL, std::string(who) + ": the slice sampler needs a device potential (not external)");
+  if (h->cfg.dim > 64) return fail(h, AMH_EINVAL, std::string(who) + ": dim must be <= 64");
+  if (!amh::pooled_asss_model(h->model_id, h->cfg.dim))
+    return fail(h, AMH_EINVAL, std::string(who) + ": no pooled slice kernel for this model and dim");
+  return AMH_OK;
+}
+
+int pooled_asss_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
+                           float* z_out, float* pe_out, double* sums, void* stream, const char* who) {
+  if (!pooled_ok(in) || !z_out || !pe_out || !sums || num_chains < 1 || k_steps < 1)
+    return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  const int cpw = amh::pooled_cpw(num_chains);
+  const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
+  const int64_t n_chunks = (num_chains + chunk - 1) / chunk;
+  if (int rc = reserve_partials(h, n_chunks, false, stream, who)) return rc;
+  amh::PooledStatsParams p{};
+  p.C = num_chains;
+  p.cpw = cpw;
+  p.d = h->cfg.dim;
+  p.i = in->i;
+  p.z = in->z;
+  p.pe = in->potential_energy;
+  p.keys = in->rng_key;
+  p.mu = in->loc;
+  p.L = in->scale;
+  p.eps = h->cfg.eps;
+  p.z_out = z_out;
+  p.pe_out = pe_out;
+  p.partials = h->partials.as<double>();
+  p.model = h->model;
+  p.k_steps = k_steps;
+  const hipError_t e = amh::run_pooled_asss_stats(h->model_id, p, sums, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+int pooled_asss_update_impl(amh_handle* h, const double* sums, const amh_pooled_state* in,
+                            const amh_pooled_state* out, int32_t k_steps, void* stream, const char* who) {
+  if (!sums || !pooled_ok(in) || !pooled_ok(out)) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  if (k_steps < 1 || h->cfg.num_warmup % k_steps != 0)
+    return fail(h, AMH_EINVAL, std::string(who) + ": k_steps must be >= 1 and divide num_warmup");
+  if (int rc = use_device(h, who)) return rc;
+  amh::PooledUpdateParams p{};
+  p.d = h->cfg.dim;
+  p.W = h->cfg.num_warmup;
+  p.a = h->cfg.lr_decay;
+  p.target = h->cfg.target_accept_prob;
+  p.sums = sums;
+  p.in = *in;
+  p.out = *out;
+  p.K = k_steps;
+  const hipError_t e = amh::run_pooled_update(p, (hipStream_t)stream, true);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amh_pooled_asss_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
+                            float* z_out, float* pe_out, double* sums, void* stream) {
+  const char* const who = "amh_pooled_asss_stats_k";
+  if (int rc = pooled_asss_enter(h, who)) return rc;
+  return pooled_asss_stats_impl(h, num_chains, in, k_steps, z_out, pe_out, sums, stream, who);
+}
+
+int amh_pooled_asss_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in,
+                             const amh_pooled_state* out, int32_t k_steps, void* stream) {
+  const char* const who = "amh_pooled_asss_update_k";
+  if (int rc = pooled_asss_enter(h, who)) return rc;
+  return pooled_asss_update_impl(h, sums, in, out, k_steps, stream, who);
+}
+
+int amh_pooled_asss_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, const amh_pooled_state* out,
+                           int32_t n_steps, int32_t sync_every, double* sums, void* stream) {
+  const char* const who = "amh_pooled_asss_step_k";
+  if (int rc = pooled_asss_enter(h, who)) return rc;
+  if (n_steps < 0 || sync_every < 1 || n_steps % sync_every != 0)
+    return fail(h, AMH_EINVAL, std::string(who) + ": n_steps must be a non-negative multiple of sync_every");
+  if (!pooled_ok(in) || !pooled_ok(out) || !sums) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  const amh_pooled_state* src = in;
+  for (int32_t t = 0; t < n_steps; t += sync_every) {
+    int rc = pooled_asss_stats_impl(h, num_chains, src, sync_every, out->z, out->potential_energy, sums, stream, who);
+    if (rc != AMH_OK) return rc;
+    rc = pooled_asss_update_impl(h, sums, src, out, sync_every, stream, who);
+    if (rc != AMH_OK) return rc;
+    src = out;
   }
   return AMH_OK;
 }

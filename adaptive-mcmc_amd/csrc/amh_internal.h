@@ -258,7 +258,12 @@ hipError_t run_kernel_sum(const float* A, int64_t n, const float* B, int64_t m, 
                           double* partials, double* out, hipStream_t s);
 hipError_t run_dist2(const float* A, int64_t n, const float* B, int64_t m, int d, float* out, hipStream_t s);
 hipError_t run_normals(uint32_t k0, uint32_t k1, int64_t n, float* out, hipStream_t s);
-hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s);
+// asss: the pooled ASSS update (log_step_size copied through, as_change of asss.py:259-260)
+hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s, bool asss = false);
+// pooled ASSS (amh_pooled_asss.hip): the slice transition against the shared
+// factor, d <= 64, registry models; p.lam is not read
+bool pooled_asss_model(int model_id, int d);
+hipError_t run_pooled_asss_stats(int model_id, const PooledStatsParams& p, double* sums, hipStream_t s);
 
 hipError_t run_step(int model_id, const StepParams& p, hipStream_t s);
 hipError_t run_lse_rows(const float* Cm, int64_t rows, int64_t cols, const float* pot, float logw, float eps,

@@ -10,7 +10,8 @@
 //                         two-level order); ranks then all-reduce them (RCCL)
 //   pooled_update_kernel  mu, Sigma, lambda, mean-accept update and the
 //                         Cholesky refactorisation of Sigma' (one wave, rows
-//                         in registers, columns broadcast through LDS, double)
+//                         in registers, columns broadcast through LDS, double);
+//                         <true>: the pooled ASSS form (amh_pooled_asss.hip)
 //
 // The order of every sum is fixed (oracle: orc_pooled_stats/_update), so the
 // result does not depend on which CU runs which chunk.
@@ -18,20 +19,6 @@
 #include "amh_pooled_device.h"
 
 namespace amh {
-
-namespace {
-
-template <template <int> class M>
-__host__ __device__ inline size_t pooled_lds_model_floats(const ModelArgs& m, int d) {
-  return (M<64>::lds_bytes(m, d) / sizeof(float) + 3) & ~(size_t)3;
-}
-template <template <int> class M>
-__host__ __device__ inline size_t pooled_lds_bytes(const ModelArgs& m, int d) {
-  const size_t f = pooled_lds_model_floats<M>(m, d) + (size_t)d * pooled_ld(d);
-  return (f + kPooledTreeFloats) * sizeof(float);
-}
-
-}  // namespace
 
 template <template <int> class M, bool EXACT>
 __global__ __launch_bounds__(kPoolWaves * 64) void pooled_stats_kernel(PooledStatsParams p) {
@@ -204,6 +191,10 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 // order, oracle mirror).
 constexpr int kUpdLd = 65;  // LDS row stride of the [r][k] staging arrays
 
+// ASSS (pooled ASSS, amh_pooled_asss.hip): no step size -- log_step_size is
+// copied through, S_a counts the chains that moved -- and as_change is
+// asss.py:259-260, ||mu' - mu||_2 + ||L' - L||_F.
+template <bool ASSS>
 __global__ __launch_bounds__(512) void pooled_update_kernel(PooledUpdateParams p) {
   const int d = p.d;
   const int tid = threadIdx.x;
@@ -242,7 +233,7 @@ __global__ __launch_bounds__(512) void pooled_update_kernel(PooledUpdateParams p
     const float lam = p.in.log_step_size[0];
     const float abar = (float)(sums[d + P] / N);
     const float maccn = macc + (abar - macc) / (float)n;
-    const float lamn = lam + gamma * (abar - p.target);
+    const float lamn = ASSS ? lam : lam + gamma * (abar - p.target);
     const float mun = act ? p.in.loc[r] + gamma * (float)(sums[r] / N) : 0.0f;
     double A[64];
     static_for<64>([&](auto K) {
@@ -275,7 +266,7 @@ __global__ __launch_bounds__(512) void pooled_update_kernel(PooledUpdateParams p
         asm volatile("" ::: "memory");
       }
     });
-    const float e0 = amh_expf(lam), e1 = amh_expf(lamn);
+    const float e0 = ASSS ? 1.0f : amh_expf(lam), e1 = ASSS ? 1.0f : amh_expf(lamn);
     float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     float* Lns = (float*)As;  // the new factor, float [r][k] (row r's doubles are already in registers)
     static_for<64>([&](auto J) {
@@ -283,12 +274,16 @@ __global__ __launch_bounds__(512) void pooled_update_kernel(PooledUpdateParams p
       if (j < d) {
         const float lo = (j <= r && act) ? Los[r * kUpdLd + j] : 0.0f;
         const float ln = ok ? (float)A[j] : lo;
-        const float tt = (j <= r && act) ? (ln * e1) - (lo * e0) : 0.0f;
+        const float tt = (j <= r && act) ? (ASSS ? ln - lo : (ln * e1) - (lo * e0)) : 0.0f;
         s4[j & 3] = fmaf(tt, tt, s4[j & 3]);
       }
     });
     const float part = act ? (s4[0] + s4[1]) + (s4[2] + s4[3]) : 0.0f;
-    const float asc = sqrtf(Grp<64>::sum(part));
+    float asc = sqrtf(Grp<64>::sum(part));
+    if constexpr (ASSS) {
+      const float dmu = act ? mun - p.in.loc[r] : 0.0f;
+      asc = sqrtf(Grp<64>::sum(dmu * dmu)) + asc;
+    }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
     static_for<64>([&](auto K) {
@@ -376,9 +371,13 @@ hipError_t run_pooled_stats(int model_id, const PooledStatsParams& p, double* su
   }
 }
 
-hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s) {
+hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s, bool asss) {
   if (p.d < 1 || p.d > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pooled_update_kernel, dim3(1), dim3(512), 0, s, p);
+  if (asss) {
+    hipLaunchKernelGGL(pooled_update_kernel<true>, dim3(1), dim3(512), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(pooled_update_kernel<false>, dim3(1), dim3(512), 0, s, p);
+  }
   return hipGetLastError();
 }
 

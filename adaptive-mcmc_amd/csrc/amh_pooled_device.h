@@ -62,6 +62,18 @@ __device__ __forceinline__ void pooled_stage_factor(float* lrow, const float* __
 constexpr int kTreeSlot = 64 * 65 / 2 + 64 + 1;
 constexpr size_t kPooledTreeFloats = (size_t)(kPoolWaves / 2) * kTreeSlot;
 
+// LDS of a lane-per-row stats block: the model's staged data (rounded up to
+// 16 bytes), the factor's d rows, the combine tree
+template <template <int> class M>
+__host__ __device__ inline size_t pooled_lds_model_floats(const ModelArgs& m, int d) {
+  return (M<64>::lds_bytes(m, d) / sizeof(float) + 3) & ~(size_t)3;
+}
+template <template <int> class M>
+__host__ __device__ inline size_t pooled_lds_bytes(const ModelArgs& m, int d) {
+  const size_t f = pooled_lds_model_floats<M>(m, d) + (size_t)d * pooled_ld(d);
+  return (f + kPooledTreeFloats) * sizeof(float);
+}
+
 // One chain-step's delta (lane r = row r; 0 in lanes r >= d) into the wave's
 // float32 sums: sd += delta_r, (S_k, S_k+1) += delta_r (delta_k, delta_k+1)
 // through one v_pk_fma_f32 per pair (each half is the same fmaf; past d the

@@ -13,10 +13,11 @@ does not shadow them (tests/test_integration.py)."""
 from .arwmh import ARWMH, ARWMHAdaptState, ARWMHState, init_to_uniform, pack_scale, packed_size, unpack_scale
 from .asss import ASSS, ASSSAdaptState, ASSSState
 from .pooled import PooledAdaptState, PooledARWMH, PooledState, pooled_chunk
+from .pooled_asss import PooledASSS
 from .random import PRNGKey, split
 from .checkpoint import load_state, load_state_dict, save_state, state_dict
 
 __all__ = ["ARWMH", "ARWMHState", "ARWMHAdaptState", "init_to_uniform", "pack_scale", "unpack_scale",
            "packed_size", "PRNGKey", "split", "PooledARWMH", "PooledState", "PooledAdaptState",
-           "pooled_chunk",
+           "pooled_chunk", "PooledASSS",
            "ASSS", "ASSSState", "ASSSAdaptState", "state_dict", "load_state_dict", "save_state", "load_state"]

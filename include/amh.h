@@ -372,6 +372,45 @@ int amh_pooled_stats_external(amh_handle* h, int64_t num_chains, const amh_poole
  * its text in amh_last_error; nothing is retried. */
 int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm, void* stream);
 
+/* ----------------------------------------------------------- pooled ASSS ----
+ * The slice sampler in regime B (build-defined): all chains
+ * share mu (loc[d]), L (scale[P]), Sigma = L L^T (cov[P], double) and i.
+ * A block is K = k_steps transitions of every chain with the shared state
+ * frozen.  Transition t of chain c is asss.py:210-244 with the shared mu and
+ * L in place of the chain's own:
+ *   S = (L + eps I) sqrt(d);  y = S^-1 (x - mu) projected to z on S^d;
+ *   tangent v orthogonal to z;  level t = U~(z) - log u;  shrinkage on
+ *   z cos(theta) + v sin(theta) for at most 50 rounds (capped, or a
+ *   degenerate tangent: theta = 0);  x' = S z'_{1:d} / (1 - z'_{d+1}) + mu;
+ *   pe' = U(x'), NaN -> +inf.
+ * Noise: the per-chain ASSS stream at position i + t with the chain's key:
+ * Philox(r, i + t, 0, TAG_ASSS) for v, v_d, u_t, theta_0 and
+ * Philox(k, i + t, 1, TAG_ASSS) for shrink round k.
+ * The sums are the pooled vector [S_d | S_dd packed | S_a | N]:
+ *   delta = x' - mu (the frozen mu),  S_d = sum delta,  S_dd = sum delta
+ *   delta^T over the block's K C chain-steps,  N = K C,  S_a = sum a with
+ *   a = 0 for a transition that kept its point (cap reached or degenerate
+ *   tangent) and 1 otherwise, so mean_accept_prob is the running share of
+ *   chain-steps that moved.
+ * The update, from the all-reduced sums (amh_pooled_allreduce as it is):
+ *   n = the block count (i / K + 1, reset at num_warmup), gamma = 1 / n^a,
+ *   mu'  = mu + gamma S_d / N,   Sig' = (1 - gamma) Sig + gamma S_dd / N,
+ *   L'   = chol(Sig') in double, rounded once (L and Sig kept if Sig' is not
+ *          positive definite),
+ *   macc' = macc + (S_a / N - macc) / n,   log_step_size copied through,
+ *   as_change = ||mu' - mu||_2 + ||L' - L||_F (asss.py:259-260),  i += K.
+ * With one chain in total this is the reference's recurrence (asss.py:246-255).
+ * Arguments, in-place aliasing and errors as amh_pooled_stats_k / _update_k /
+ * _step_k.  d <= 64 and a device potential (Gaussian, eight schools, kidiq,
+ * diamonds, diamonds_suffstat): AMH_EINVAL otherwise. */
+int amh_pooled_asss_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
+                            float* z_out, float* pe_out, double* sums, void* stream);
+int amh_pooled_asss_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in,
+                             const amh_pooled_state* out, int32_t k_steps, void* stream);
+int amh_pooled_asss_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in,
+                           const amh_pooled_state* out, int32_t n_steps, int32_t sync_every, double* sums,
+                           void* stream);
+
 /* -------------------------------------------------------- exact sums ----
  * The sums above are added in double, in an order that depends on how many
  * chunks a rank holds, so two partitions of the same chains over ranks round
