@@ -13,15 +13,21 @@ namespace amh {
 
 // Diagnostic build only (-DAMH_STAMPS; tools/s64_tail.py, tools/s64_phases.py):
 // one record per wave on the constant 100 MHz clock, read back with
-// amh_diag_s64_stamps() -- [start, end, items, block, phase (a) .. (d) totals].
+// amh_diag_s64_stamps() -- [start, end, items, block, phase (a) .. (d) totals,
+// the ARWMH compute phase's parts: noise, proposal, potential, accept +
+// schedule, sweep 1 + coefficients, sweep 2 (each stamp is a scalar-memory
+// round trip of its own: the parts sum to more than the release build's (d))].
 #ifdef AMH_STAMPS
 constexpr int kS64StampWaves = 1 << 16;
-constexpr int kS64StampSlots = 8;
+constexpr int kS64StampSlots = 16;
+constexpr int kS64SubPhases = 6;
 __device__ unsigned long long g_s64_stamps[kS64StampWaves * kS64StampSlots];
 hipError_t diag_s64_stamps_copy(void* host, size_t bytes) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_s64_stamps), bytes, 0, hipMemcpyDeviceToHost);
 }
-#define AMH_S64_PHASE_INIT unsigned long long st_ph[4] = {0, 0, 0, 0}, st_pt = 0;
+#define AMH_S64_PHASE_INIT                                  \
+  unsigned long long st_ph[4] = {0, 0, 0, 0}, st_pt = 0; \
+  S64Sub st_sub = {{0, 0, 0, 0, 0, 0}, 0};
 #define AMH_S64_PHASE_MARK st_pt = __builtin_amdgcn_s_memrealtime();
 #define AMH_S64_PHASE(k)                                             \
   {                                                                  \
@@ -29,10 +35,26 @@ hipError_t diag_s64_stamps_copy(void* host, size_t bytes) {
     st_ph[k] += t_ - st_pt;                                          \
     st_pt = t_;                                                      \
   }
+struct S64Sub {
+  unsigned long long ph[kS64SubPhases], pt;
+};
+#define AMH_S64_SUB_PARAM , S64Sub& st_sub
+#define AMH_S64_SUB_ARG , st_sub
+#define AMH_S64_SUB_MARK st_sub.pt = __builtin_amdgcn_s_memrealtime();
+#define AMH_S64_SUB(k)                                               \
+  {                                                                  \
+    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();  \
+    st_sub.ph[k] += t_ - st_sub.pt;                                  \
+    st_sub.pt = t_;                                                  \
+  }
 #else
 #define AMH_S64_PHASE_INIT
 #define AMH_S64_PHASE_MARK
 #define AMH_S64_PHASE(k)
+#define AMH_S64_SUB_PARAM
+#define AMH_S64_SUB_ARG
+#define AMH_S64_SUB_MARK
+#define AMH_S64_SUB(k)
 #endif
 
 // ------------------------------------------------------ d = 64 step kernel --
@@ -53,12 +75,17 @@ hipError_t diag_s64_stamps_copy(void* host, size_t bytes) {
 //   chain; sweep 1 runs on lanes r > j, so lane r keeps its w_r when its own
 //   column passes -- that is the forward-solve value the general kernel
 //   captures with a v_writelane per column.
-// * Broadcasts from LDS.  The per-column values every lane needs (dl_j and
-//   1/l_j in the swap, eta_j of the proposal, diff_j of the potential, and the
-//   four coefficients of sweep 2) are written once per lane into a 1 KiB
-//   per-wave scratch and read back four columns at a time with broadcast
-//   ds_read_b128, in place of v_readlane + s_nop per column.  Only sweep 1,
-//   whose w_j is serial, still uses v_readlane.
+// * Broadcasts.  The per-column values every lane needs (dl_j and 1/l_j in
+//   the swap, eta_j of the proposal, diff_j of the potential, and the four
+//   coefficients of sweep 2) are written once per lane into a 1 KiB per-wave
+//   scratch and read back four columns at a time with broadcast ds_read_b128,
+//   in place of v_readlane + s_nop per column.  Sweep 1, whose w_j is serial,
+//   uses v_readlane.  A single-step ARWMH launch takes eta and diff through
+//   scalar registers instead (s64_lanes, s64_matvec_sg, s64_gauss_pot_sg): its
+//   compute phase runs beside the factor traffic and is bound by latency per
+//   wave, where an LDS round trip costs the launch 0.25 us and a batch of
+//   v_readlane has no wait.  A fused launch is bound by VALU issue and lost
+//   6 % with them; ASSS gained nothing.
 constexpr int kS64Waves = 16;
 // Cache policy of this kernel's factor traffic (its own: kLoadAux / kStoreAux
 // serve the other kernels), by the chain's place in the block's schedule
@@ -101,9 +128,11 @@ __device__ __forceinline__ void s64_store_policy(int cls, F&& f) {
     else f(integral_constant<int, kS64StoreAuxMid>{});
   }
 }
-constexpr int kS64EB = 8;  // proposal: broadcast columns per LDS wait
-constexpr int kS64PB = 8;  // potential: columns per LDS wait
+constexpr int kS64EB = 8;   // proposal: broadcast columns per LDS wait / per batch of scalar registers
+constexpr int kS64PB = 8;   // potential, vector from the scratch: columns per LDS wait
+constexpr int kS64PG = 16;  // potential, vector in scalar registers: columns per LDS wait and per batch
 static_assert(kS64EB == 8 && kS64PB == 8, "the batch readers (lds_ld4x2w / lds_ld4x4w) read two quarter-vectors per stream");
+static_assert(kS64PG == 16, "s64_gauss_pot_sg waits for four quarter-rows; s64_lanes takes 8 or 16");
 typedef uint32_t uint32x4_t_ __attribute__((ext_vector_type(4)));
 constexpr int kS64P = 2080;                   // d(d+1)/2
 constexpr int kS64Z = 2080, kS64M = 2144, kS64S = 2208, kS64X = 2216;  // wave-buffer offsets (floats)
@@ -147,7 +176,7 @@ static_assert(s64_piece_group(0) == 1 && s64_piece_group(4) == 6 && s64_piece_gr
               "the table of DESIGN.md 3.1");
 
 // The swap's group of four columns j = 4 G .. 4 G + 3 as whole statements:
-// one s_lshl_b64 exec per mask and ONE exec restore per statement, where a
+// one s_lshl_b64 exec per mask and ONE exec restore per masked statement, where a
 // statement per masked operation saves, shifts and restores exec around it
 // and has hipcc's boundary pad after it (80 instructions per group).  exec is
 // restored with s_mov_b64 exec, -1 and not from a saved pair (no SGPR pair
@@ -158,21 +187,26 @@ static_assert(s64_piece_group(0) == 1 && s64_piece_group(4) == 6 && s64_piece_gr
 // -> DS read of it as data.
 //
 // s64_group_read: [dl | 1/l] quarter-vectors of the group, the piece the
-// previous group finished (MP >= 0: 16 B per lane at la16), column j of the
-// incoming factor on lanes r > j, in that order, and their one wait.  t[k]
-// is written on lanes r > j only and is consumed under the same mask only.
-#define AMH_SWG_RD(k) "s_lshl_b64 exec, -1, %[m" #k "]\n\tds_read_b32 %[t" #k "], %[la] offset:%[o" #k "]\n\t"
+// previous group finished (MP >= 0: 16 B per lane at la16), the group's
+// columns of the incoming factor, in that order, and their one wait.  The
+// column reads carry no mask: column j's address la + (s64_col(j) - j) 4 lies
+// inside the wave buffer for every lane (s64_col(j) >= j, and lane 63 of
+// column 63 is the factor's last float), and t[k] is consumed on lanes r > j
+// only (s64_group_norm), so what the lanes r <= j read is never used -- one
+// s_lshl_b64 exec per column less than the masked read.
+#define AMH_SWG_RD(k) "ds_read_b32 %[t" #k "], %[la] offset:%[o" #k "]\n\t"
 #define AMH_SWG_RD_HEAD "ds_read_b128 %[dl], %[zm] offset:%[od]\n\tds_read_b128 %[in], %[zm] offset:%[oi]\n\t"
 #define AMH_SWG_RD_PIECE "ds_read_b128 %[pv], %[lp] offset:%[op]\n\t"
-#define AMH_SWG_RD_TAIL "s_mov_b64 exec, -1\n\ts_waitcnt lgkmcnt(0)"
+#define AMH_SWG_RD_TAIL "s_waitcnt lgkmcnt(0)"
 template <int G, int MP>
 __device__ __forceinline__ void s64_group_read(f32x4& dl4, f32x4& in4, f32x4& pv, float (&t)[4], uint32_t zm_a,
                                                uint32_t la16, uint32_t la) {
   constexpr int j = 4 * G;
   static_assert(G < 15 || MP >= 0, "the last group reads the piece that group 14 finished");
-#define AMH_SWG_RD_OPS3                                                                                       \
-  [zm] "v"(zm_a), [la] "v"(la), [od] "n"(16 * G), [oi] "n"(256 + 16 * G), [m0] "n"(j + 1), [m1] "n"(j + 2), \
-      [m2] "n"(j + 3), [o0] "n"((s64_col(j) - j) * 4), [o1] "n"((s64_col(j + 1) - (j + 1)) * 4),             \
+  static_assert(s64_col(j) >= j && s64_col(j + 3) - (j + 3) + 63 < kS64P, "unmasked column reads stay inside the factor");
+#define AMH_SWG_RD_OPS3                                                                          \
+  [zm] "v"(zm_a), [la] "v"(la), [od] "n"(16 * G), [oi] "n"(256 + 16 * G),                       \
+      [o0] "n"((s64_col(j) - j) * 4), [o1] "n"((s64_col(j + 1) - (j + 1)) * 4),                 \
       [o2] "n"((s64_col(j + 2) - (j + 2)) * 4)
   if constexpr (G == 15) {  // column 63 has nothing below its diagonal
     asm volatile(AMH_SWG_RD_HEAD AMH_SWG_RD_PIECE AMH_SWG_RD(0) AMH_SWG_RD(1) AMH_SWG_RD(2) AMH_SWG_RD_TAIL
@@ -184,13 +218,12 @@ __device__ __forceinline__ void s64_group_read(f32x4& dl4, f32x4& in4, f32x4& pv
                      AMH_SWG_RD_TAIL
                  : [dl] "=&v"(dl4), [in] "=&v"(in4), [pv] "=&v"(pv), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]),
                    [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
-                 : AMH_SWG_RD_OPS3, [m3] "n"(j + 4), [o3] "n"((s64_col(j + 3) - (j + 3)) * 4), [lp] "v"(la16),
-                   [op] "n"(1024 * MP));
+                 : AMH_SWG_RD_OPS3, [o3] "n"((s64_col(j + 3) - (j + 3)) * 4), [lp] "v"(la16), [op] "n"(1024 * MP));
   } else {
     asm volatile(AMH_SWG_RD_HEAD AMH_SWG_RD(0) AMH_SWG_RD(1) AMH_SWG_RD(2) AMH_SWG_RD(3) AMH_SWG_RD_TAIL
                  : [dl] "=&v"(dl4), [in] "=&v"(in4), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]),
                    [t3] "=&v"(t[3])
-                 : AMH_SWG_RD_OPS3, [m3] "n"(j + 4), [o3] "n"((s64_col(j + 3) - (j + 3)) * 4));
+                 : AMH_SWG_RD_OPS3, [o3] "n"((s64_col(j + 3) - (j + 3)) * 4));
   }
 #undef AMH_SWG_RD_OPS3
 }
@@ -337,10 +370,78 @@ __device__ __forceinline__ float s64_keep_at(float old, float v) {
   return out;
 }
 
-// U h, h one element per lane: lane r writes h_r to the wave's scratch x_a and
-// reads the vector back kS64EB columns per LDS wait (16-B broadcast reads).
-// WAIT: every lane's reads are done before the caller writes the scratch
-// again (the wait sits before the final sums, as the ASSS transition had it).
+// Lanes J0 .. J0 + N - 1 of v in scalar registers (v_readlane at immediate
+// lanes): how the proposal and the potential of a single-step ARWMH launch
+// broadcast their vector -- no scratch write, no broadcast LDS reads, no wait;
+// the FMAs take the scalar operand.  The batch's v_readlane stand together in
+// front of the pin and the
+// uses behind it, so a VALU read of an SGPR that v_readlane wrote (two wait
+// states, s64_sweep1x8) has them from the batch itself but possibly the first
+// use, which the compiler pads.  The values are bit copies: NaN payloads,
+// signed zeros and denormals arrive as they are.
+template <int J0, int N>
+__device__ __forceinline__ void s64_lanes(float v, float (&s)[N]) {
+  static_assert(N == 8 || N == 16, "batches of 8 or 16 lanes");
+  static_for<N>([&](auto K) { s[(int)K] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), J0 + K)); });
+  if constexpr (N == 8) {
+    asm volatile("" : "+s"(s[0]), "+s"(s[1]), "+s"(s[2]), "+s"(s[3]), "+s"(s[4]), "+s"(s[5]), "+s"(s[6]), "+s"(s[7]));
+  } else {
+    asm volatile("" : "+s"(s[0]), "+s"(s[1]), "+s"(s[2]), "+s"(s[3]), "+s"(s[4]), "+s"(s[5]), "+s"(s[6]), "+s"(s[7]),
+                 "+s"(s[8]), "+s"(s[9]), "+s"(s[10]), "+s"(s[11]), "+s"(s[12]), "+s"(s[13]), "+s"(s[14]), "+s"(s[15]));
+  }
+}
+
+// U h, h one element per lane, kS64EB columns per batch of scalar registers.
+__device__ __forceinline__ float s64_matvec_sg(const float (&U)[64], float h) {
+  float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  static_for<64 / kS64EB>([&](auto B) {
+    constexpr int b = B;
+    float e[kS64EB];
+    s64_lanes<kS64EB * b>(h, e);
+    static_for<kS64EB>([&](auto K) {
+      constexpr int j = kS64EB * b + K;
+      a4[j & 3] = fmaf(U[j], e[(int)K], a4[j & 3]);
+    });
+    __builtin_amdgcn_sched_barrier(0);
+  });
+  return (a4[0] + a4[1]) + (a4[2] + a4[3]);
+}
+
+// The d = 64 Gaussian potential (GaussianM<64>::potential, the same float
+// operations and order): kS64PG columns of this lane's row of P per LDS wait,
+// diff_j in even-aligned scalar pairs for the packed FMAs, moved there while
+// the row's reads are in flight.
+__device__ __forceinline__ float s64_gauss_pot_sg(float diff, uint32_t prow, float c0) {
+  f32x2v y01 = {0.0f, 0.0f}, y23 = {0.0f, 0.0f};
+  static_for<64 / kS64PG>([&](auto B) {
+    constexpr int b = B;
+    constexpr int NQ = kS64PG / 4;
+    f32x4 pv[NQ];
+    static_for<NQ>([&](auto Q) { pv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(prow); });
+    float dv[kS64PG];
+    s64_lanes<kS64PG * b>(diff, dv);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]));
+    static_for<2 * NQ>([&](auto K2) {
+      const f32x4 q = pv[(int)K2 / 2];
+      const f32x2v pp = (K2 % 2 == 0) ? f32x2v{q[0], q[1]} : f32x2v{q[2], q[3]};
+      const f32x2v bp = {dv[2 * (int)K2], dv[2 * (int)K2 + 1]};
+      if constexpr (K2 % 2 == 0) {
+        y01 = __builtin_elementwise_fma(pp, bp, y01);
+      } else {
+        y23 = __builtin_elementwise_fma(pp, bp, y23);
+      }
+    });
+    __builtin_amdgcn_sched_barrier(0);
+  });
+  const float y = (y01[0] + y01[1]) + (y23[0] + y23[1]);
+  const float S = Grp<64>::sum(diff * y);
+  return (0.5f * S) + c0;
+}
+
+// U h through the wave's scratch: lane r writes h_r to x_a and reads the vector
+// back kS64EB columns per LDS wait (16-B broadcast reads).  WAIT: every lane's
+// reads are done before the caller writes the scratch again (the wait sits
+// before the final sums, as the ASSS transition had it).
 template <bool WAIT = false>
 __device__ __forceinline__ float s64_matvec(const float (&U)[64], float h, uint32_t x_a, uint32_t r) {
   s64_wr(x_a + r * 4u, h);
@@ -583,26 +684,32 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
 // One ARWMH transition (arwmh.py:140-207) on the d = 64 persistent kernel's
 // registers: the same float operations in the same order as
 // arwmh_step_kernel<64, GaussianM, true> (oracle: orc_step), with the column
-// broadcasts read from the wave's LDS scratch.
+// broadcasts read from the wave's LDS scratch or, sg (wave-uniform: a
+// single-step launch), the proposal's and the potential's from scalar registers.
 __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&U)[64], float& dl, float& z, float& mu,
                                                    float& pe, float& macc, float& lam, float& asc, bool& updated,
                                                    int32_t& nacc, int32_t it, uint32_t k0, uint32_t k1, int r,
                                                    const GaussianM<64>::Ctx& mctx, uint32_t x_a, uint32_t xq_a,
-                                                   uint32_t prow) {
+                                                   uint32_t prow, bool sg AMH_S64_SUB_PARAM) {
   using Gp = Grp<64>;
+  AMH_S64_SUB_MARK
   // ---- noise (arwmh.py:162-165, 174): stream position = state.i
   float xi, u;
   step_noise_w64(r, (uint32_t)it, k0, k1, xi, u);  // bit spec: amh_step_word
 
+  AMH_S64_SUB(0)
   // ---- proposal z' = z + (L e^lam + eps I) xi  (arwmh.py:166-167), L xi = U (dl * xi)
   const float el = amh_expf(lam);
   const float eta = dl * xi;
-  const float acc = s64_matvec(U, eta, x_a, (uint32_t)r);
+  const float acc = sg ? s64_matvec_sg(U, eta) : s64_matvec(U, eta, x_a, (uint32_t)r);
   const float zp = z + fmaf(el, acc, p.eps * xi);
 
-  // ---- potential (GaussianM<64>::potential with diff_j from the scratch), NaN -> +inf
-  float pep = s64_gauss_pot(zp - mctx.mr, x_a, prow, (uint32_t)r, mctx.c0);
+  AMH_S64_SUB(1)
+  // ---- potential (GaussianM<64>::potential with diff_j from the scratch or scalar registers), NaN -> +inf
+  float pep = sg ? s64_gauss_pot_sg(zp - mctx.mr, prow, mctx.c0)
+                 : s64_gauss_pot(zp - mctx.mr, x_a, prow, (uint32_t)r, mctx.c0);
   if (amh_isnan(pep)) pep = INFINITY;
+  AMH_S64_SUB(2)
 
   // ---- accept / reject (arwmh.py:173-178)
   const float ex = amh_expf(pe - pep);
@@ -630,11 +737,13 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
   const float Dg = ajj * ajj;
   const float one = (amh_isfinite(ajj) && ajj != 0.0f) ? 1.0f : __int_as_float(0x7FC00000);
 
+  AMH_S64_SUB(3)
   // sweep 1 (lanes r > j): afterwards lane r holds w*_r (forward solve U w* = delta)
   float ws = delta;
   s64_sweep1_all(ws, U);
 
   const S64Coef k = s64_rank_one_coef(ws, Dg, one, gamma, r);
+  AMH_S64_SUB(4)
   if (!k.revert) {
     // sweep 2 with the as_change terms U_rj (q_j e1 - dl_j e0) + (c_j q_j e1) w_r^{(j+1)}
     const float ac = (k.q * e1) - (dl * el);
@@ -655,6 +764,7 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
     asc = sqrtf(Gp::sum(sacc));
   }
 
+  AMH_S64_SUB(5)
   // ---- commit (arwmh.py:199-207); the caller advances `it`
   z = zn;
   pe = pen;
@@ -904,7 +1014,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       constexpr int g = G4;
       constexpr int mp = g > 0 ? s64_piece_after(g - 1) : -1;  // the piece the previous group finished
       f32x4 dl4, in4, pv;
-      float t[4];  // no initial value: lanes a column does not read are never consumed
+      float t[4];  // no initial value: what lanes r <= j hold is never consumed
       s64_group_read<g, mp>(dl4, in4, pv, t, zm_a, la16, la);
       if (wr) {
         if constexpr (mp >= 0) {
@@ -944,11 +1054,13 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 
     nacc = 0;
     bool updated = false;
+    const bool sg = p.n_steps == 1;  // the proposal's and the potential's vector: s64_lanes or the scratch
     for (int32_t t = 0; t < p.n_steps; ++t) {
       if constexpr (kASSS) {
         asss_transition64(p, U, dl, z, mu, pe, asc, updated, it, k0, k1, r, mctx, x_a, xq_a, prow);
       } else {
-        arwmh_transition64(p, U, dl, z, mu, pe, macc, lam, asc, updated, nacc, it, k0, k1, r, mctx, x_a, xq_a, prow);
+        arwmh_transition64(p, U, dl, z, mu, pe, macc, lam, asc, updated, nacc, it, k0, k1, r, mctx, x_a, xq_a, prow,
+                           sg AMH_S64_SUB_ARG);
       }
       it += 1;
       if (p.col_z != nullptr || p.col_pe != nullptr) {
@@ -998,6 +1110,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
       row[2] = (unsigned long long)st_items;
       row[3] = (unsigned long long)blockIdx.x;
       for (int k_ = 0; k_ < 4; ++k_) row[4 + k_] = st_ph[k_];
+      for (int k_ = 0; k_ < kS64SubPhases; ++k_) row[8 + k_] = st_sub.ph[k_];
     }
   }
 #endif

@@ -5,7 +5,10 @@ adaptive-mcmc_amd/csrc stamps):
   (a) the vmcnt(0) wait for the chain's DMA at the top of the loop,
   (b) hand-over start -> first factor store issued,
   (c) -> last DMA of the next chain issued (and the next ticket drawn),
-  (d) compute.
+  (d) compute, and its parts in the ARWMH transition: noise, proposal,
+      potential, accept + schedule (with gamma), sweep 1 + coefficients, sweep 2
+      (every stamp is a scalar-memory round trip: the parts carry their own
+      cost and (d) is longer than in the release build).
 Prints, per launch, the mean per iteration and the share of the loop of each
 phase, and the spread over waves.  Usage (GPU box): python3 tools/s64_phases.py
 (AMH_LIB_PATH selects another stamps build)."""
@@ -32,11 +35,12 @@ st = k.init(PRNGKey(0), 0, (torch.rand(C, d, device=dev) * 4 - 2).contiguous(), 
 for _ in range(300):
     k.sample_(st, 1)
 torch.cuda.synchronize()
-W, S = 1 << 16, 8
+W, S = 1 << 16, 16
 L = _lib.lib()
 L.amh_diag_s64_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
 print(f"library {os.environ['AMH_LIB_PATH']}")
 NAMES = ["(a) wait", "(b) ->1st store", "(c) ->last DMA", "(d) compute"]
+SUB = ["noise", "proposal", "potential", "accept + gamma", "sweep 1 + coef", "sweep 2"]
 for rep in range(3):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -59,4 +63,10 @@ for rep in range(3):
         per = tot[:, i] / np.maximum(items, 1)
         q = np.quantile(per, [0.1, 0.5, 0.9])
         print(f"  {n:16s} {tot[:, i].mean():7.1f} us per wave = {100 * tot[:, i].sum() / loop.sum():5.1f} % of the loop; "
+              f"per iteration mean {per.mean():6.2f} us, 10/50/90 % of waves {q[0]:.2f} / {q[1]:.2f} / {q[2]:.2f}")
+    sub = ph[:, 8:14].astype(np.float64) * 10e-3
+    for i, n in enumerate(SUB):
+        per = sub[:, i] / np.maximum(items, 1)
+        q = np.quantile(per, [0.1, 0.5, 0.9])
+        print(f"    (d) {n:14s} {100 * sub[:, i].sum() / max(tot[:, 3].sum(), 1e-9):5.1f} % of (d); "
               f"per iteration mean {per.mean():6.2f} us, 10/50/90 % of waves {q[0]:.2f} / {q[1]:.2f} / {q[2]:.2f}")

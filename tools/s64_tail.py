@@ -27,7 +27,7 @@ st = k.init(PRNGKey(0), 0, (torch.rand(C, d, device=dev) * 4 - 2).contiguous(), 
 for _ in range(300):
     st = k.sample(st, (), {})
 torch.cuda.synchronize()
-W, S = 1 << 16, 8
+W, S = 1 << 16, 16
 L = _lib.lib()
 L.amh_diag_s64_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
 for rep in range(3):
