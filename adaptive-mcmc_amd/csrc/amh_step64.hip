@@ -76,11 +76,13 @@ struct S64Sub {
 //   column passes -- that is the forward-solve value the general kernel
 //   captures with a v_writelane per column.
 // * Broadcasts.  The per-column values every lane needs (dl_j and 1/l_j in
-//   the swap, eta_j of the proposal, diff_j of the potential, and the four
-//   coefficients of sweep 2) are written once per lane into a 1 KiB per-wave
-//   scratch and read back four columns at a time with broadcast ds_read_b128,
-//   in place of v_readlane + s_nop per column.  Sweep 1, whose w_j is serial,
-//   uses v_readlane.  A single-step ARWMH launch takes eta and diff through
+//   the swap, eta_j of the proposal, diff_j of the potential) are written once
+//   per lane into a 1 KiB per-wave scratch and read back four columns at a
+//   time with broadcast ds_read_b128, in place of v_readlane + s_nop per
+//   column.  Sweep 1, whose w_j is serial, uses v_readlane.  Sweep 2's four
+//   coefficients per column go through the scratch a quarter at a time into
+//   every row of 16 lanes and reach the FMAs as DPP row broadcasts
+//   (s64_rows_quarter, s64_sweep2_group).  A single-step ARWMH launch takes eta and diff through
 //   scalar registers instead (s64_lanes, s64_matvec_sg, s64_gauss_pot_sg): its
 //   compute phase runs beside the factor traffic and is bound by latency per
 //   wave, where an LDS round trip costs the launch 0.25 us and a batch of
@@ -338,15 +340,6 @@ __device__ __forceinline__ void s64_sweep1_all(float& w, const float (&U)[64]) {
   });
 }
 
-// lanes 16Q .. 16Q+15 write v0..v3 at a, a+64, a+128, a+192 (a = scratch + 4 (r mod 16))
-template <int Q>
-__device__ __forceinline__ void s64_wr4_quarter(uint32_t a, float v0, float v1, float v2, float v3) {
-  uint64_t sv;
-  asm volatile("s_mov_b64 %0, exec\n\ts_bfm_b64 exec, 16, %6\n\tds_write_b32 %1, %2\n\t"
-               "ds_write_b32 %1, %3 offset:64\n\tds_write_b32 %1, %4 offset:128\n\t"
-               "ds_write_b32 %1, %5 offset:192\n\ts_mov_b64 exec, %0"
-               : "=&s"(sv) : "v"(a), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "n"(16 * Q) : "memory");
-}
 __device__ __forceinline__ void s64_wr(uint32_t a, float v) {  // this lane's dword at a
   asm volatile("ds_write_b32 %0, %1" : : "v"(a), "v"(v) : "memory");
 }
@@ -508,30 +501,66 @@ __device__ __forceinline__ S64Coef s64_rank_one_coef(float ws, float Dg, float o
   const float dnew = fmaf(c, 0.0f, one) * q;
   return {Gp::any(amh_isnan(dnew)), c, q};
 }
+// Quarter Q of the four coefficient vectors to every row of 16 lanes: lanes
+// 16Q .. 16Q+15 write v0..v3 at a, a+64, a+128, a+192 (a = scratch + 4 (r mod
+// 16)) and every lane reads its slot back, so that lane r holds the values of
+// lane 16Q + r mod 16 (LDS is in order within a wave); one round trip.
+template <int Q>
+__device__ __forceinline__ void s64_rows_quarter(uint32_t a, float v0, float v1, float v2, float v3, float& o0,
+                                                 float& o1, float& o2, float& o3) {
+  uint64_t sv;
+  asm volatile("s_mov_b64 %[sv], exec\n\ts_bfm_b64 exec, 16, %[q]\n\tds_write_b32 %[a], %[v0]\n\t"
+               "ds_write_b32 %[a], %[v1] offset:64\n\tds_write_b32 %[a], %[v2] offset:128\n\t"
+               "ds_write_b32 %[a], %[v3] offset:192\n\ts_mov_b64 exec, %[sv]\n\t"
+               "ds_read_b32 %[o0], %[a]\n\tds_read_b32 %[o1], %[a] offset:64\n\t"
+               "ds_read_b32 %[o2], %[a] offset:128\n\tds_read_b32 %[o3], %[a] offset:192\n\t"
+               "s_waitcnt lgkmcnt(0)"
+               : [sv] "=&s"(sv), [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3)
+               : [a] "v"(a), [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3), [q] "n"(16 * Q)
+               : "memory");
+}
+// Columns j = 4 G .. 4 G + 3 of sweep 2, the coefficients of column j taken from
+// lane j mod 16 of the lane's own row (DPP row_newbcast on the first source
+// of v_fmac / v_mul: no broadcast instruction of its own).  Per column
+//   w  = fma(-ws_j, u, w);  t = bc_j w;  t = fma(ac_j, u, t);  u = fma(c_j, w, u)
+// -- the generic kernel's operations with the factors of a product swapped:
+// the same bits.  The s_nop 1 are the two wait states of a DPP read of a VGPR
+// that a VALU wrote, should the compiler have copied a coefficient in front
+// of the statement; inside it the DPP operands are never written.
+#define AMH_SW2_COL(k)                                                                              \
+  "v_fmac_f32_dpp %[w], -%[cw], %[u" #k "] row_newbcast:%[l" #k "] row_mask:0xf bank_mask:0xf\n\t"  \
+  "v_mul_f32_dpp %[t" #k "], %[cb], %[w] row_newbcast:%[l" #k "] row_mask:0xf bank_mask:0xf\n\t"    \
+  "v_fmac_f32_dpp %[t" #k "], %[ca], %[u" #k "] row_newbcast:%[l" #k "] row_mask:0xf bank_mask:0xf\n\t" \
+  "v_fmac_f32_dpp %[u" #k "], %[cc], %[w] row_newbcast:%[l" #k "] row_mask:0xf bank_mask:0xf\n\t"
+template <int G>
+__device__ __forceinline__ void s64_sweep2_group(float (&U)[64], float& w, float (&t)[4], float cw, float cc, float ca,
+                                                 float cb) {
+  constexpr int j = 4 * G, l = j % 16;
+  asm("s_nop 1\n\t" AMH_SW2_COL(0) AMH_SW2_COL(1) AMH_SW2_COL(2) AMH_SW2_COL(3)
+      : [w] "+v"(w), [u0] "+v"(U[j]), [u1] "+v"(U[j + 1]), [u2] "+v"(U[j + 2]), [u3] "+v"(U[j + 3]), [t0] "=&v"(t[0]),
+        [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
+      : [cw] "v"(cw), [cc] "v"(cc), [ca] "v"(ca), [cb] "v"(cb), [l0] "n"(l), [l1] "n"(l + 1), [l2] "n"(l + 2),
+        [l3] "n"(l + 3));
+}
+#undef AMH_SW2_COL
 // Sweep 2 of the rank-one update: U'_rj = U_rj + c_j w_r^{(j+1)} in 16 groups of
-// four columns, the coefficient vectors (this lane's ws, c, ac, bc) through the
-// quarter-vector scratch.  Returns the wave sum of the as_change terms
-// (U_rj ac_j + bc_j w_r^{(j+1)})^2; ac and bc are where the transitions differ.
+// four columns, the coefficient vectors (this lane's ws, c, ac, bc) a quarter
+// at a time to every row through the quarter-vector scratch: four LDS round
+// trips per item and no broadcast read (the broadcast 16-B reads it replaces
+// took sixteen, and 64 ds_read_b128).  Returns the wave sum of the as_change
+// terms (U_rj ac_j + bc_j w_r^{(j+1)})^2; ac and bc are where the transitions
+// differ.
 __device__ __forceinline__ float s64_sweep2(float (&U)[64], float delta, float ws, float c, float ac, float bc,
-                                            uint32_t x_a, uint32_t xq_a) {
+                                            uint32_t xq_a) {
   float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float w = delta;
+  float cw = 0.0f, cc = 0.0f, ca = 0.0f, cb = 0.0f;
   static_for<16>([&](auto G4) {
     constexpr int g = G4;
-    // the four coefficient vectors of columns 16(g/4) .. +15 (lanes of that quarter write)
-    if constexpr (g % 4 == 0) s64_wr4_quarter<g / 4>(xq_a, ws, c, ac, bc);
-    constexpr int gq = g % 4;
-    f32x4 cw, cc, ca, cb;
-    lds_ld4x4w<16 * gq, 64 + 16 * gq, 128 + 16 * gq, 192 + 16 * gq>(cw, cc, ca, cb, x_a, x_a);
-    static_for<4>([&](auto Q) {
-      constexpr int j = 4 * g + Q;
-      const float uo = U[j];
-      w = fmaf(-cw[(int)Q], uo, w);
-      const float un = fmaf(cc[(int)Q], w, uo);
-      const float tt = fmaf(uo, ca[(int)Q], cb[(int)Q] * w);
-      s4[j & 3] = fmaf(tt, tt, s4[j & 3]);
-      U[j] = un;
-    });
+    if constexpr (g % 4 == 0) s64_rows_quarter<g / 4>(xq_a, ws, c, ac, bc, cw, cc, ca, cb);
+    float t[4];
+    s64_sweep2_group<g>(U, w, t, cw, cc, ca, cb);
+    static_for<4>([&](auto Q) { s4[(int)Q] = fmaf(t[(int)Q], t[(int)Q], s4[(int)Q]); });
     column_fence<g, 2>();
   });
   const float sacc = (s4[0] + s4[1]) + (s4[2] + s4[3]);
@@ -671,7 +700,7 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
   const S64Coef k = s64_rank_one_coef(ws, Dg, one, gamma, r);
   float sdiff = 0.0f;
   if (!k.revert) {
-    sdiff = sqrtf(s64_sweep2(U, delta, ws, k.c, k.q - dl, k.c * k.q, x_a, xq_a));
+    sdiff = sqrtf(s64_sweep2(U, delta, ws, k.c, k.q - dl, k.c * k.q, xq_a));
     dl = k.q;
     updated = true;
   }
@@ -685,12 +714,14 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
 // registers: the same float operations in the same order as
 // arwmh_step_kernel<64, GaussianM, true> (oracle: orc_step), with the column
 // broadcasts read from the wave's LDS scratch or, sg (wave-uniform: a
-// single-step launch), the proposal's and the potential's from scalar registers.
+// single-step launch: its own instance of the kernel), the proposal's and the
+// potential's from scalar registers.
+template <bool sg>
 __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&U)[64], float& dl, float& z, float& mu,
                                                    float& pe, float& macc, float& lam, float& asc, bool& updated,
                                                    int32_t& nacc, int32_t it, uint32_t k0, uint32_t k1, int r,
                                                    const GaussianM<64>::Ctx& mctx, uint32_t x_a, uint32_t xq_a,
-                                                   uint32_t prow, bool sg AMH_S64_SUB_PARAM) {
+                                                   uint32_t prow AMH_S64_SUB_PARAM) {
   using Gp = Grp<64>;
   AMH_S64_SUB_MARK
   // ---- noise (arwmh.py:162-165, 174): stream position = state.i
@@ -748,7 +779,7 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
     // sweep 2 with the as_change terms U_rj (q_j e1 - dl_j e0) + (c_j q_j e1) w_r^{(j+1)}
     const float ac = (k.q * e1) - (dl * el);
     const float bc = (k.c * k.q) * e1;
-    asc = sqrtf(s64_sweep2(U, delta, ws, k.c, ac, bc, x_a, xq_a));
+    asc = sqrtf(s64_sweep2(U, delta, ws, k.c, ac, bc, xq_a));
     dl = k.q;
     updated = true;
   } else {
@@ -776,8 +807,12 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
 // kASSS: the same persistent data movement around one ASSS transition
 // (asss_transition, amh_asss.h; asss.py:197-251) instead of the ARWMH one --
 // the state is the same but for mean_accept_prob / log_step_size (absent).
-template <int WPB, bool kASSS = false>
+// kSG: a single-step ARWMH launch (p.n_steps == 1, run_step64), whose proposal
+// and potential broadcast through scalar registers: an instance of its own, so
+// that neither instance carries the other's forms behind a branch.
+template <int WPB, bool kASSS = false, bool kSG = false>
 __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
+  static_assert(!(kASSS && kSG), "the scalar-register forms are ARWMH's");
   const StepParams& p_outer = p;
   constexpr int D = 64;
   constexpr uint32_t P = kS64P;
@@ -1054,13 +1089,12 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 
     nacc = 0;
     bool updated = false;
-    const bool sg = p.n_steps == 1;  // the proposal's and the potential's vector: s64_lanes or the scratch
     for (int32_t t = 0; t < p.n_steps; ++t) {
       if constexpr (kASSS) {
         asss_transition64(p, U, dl, z, mu, pe, asc, updated, it, k0, k1, r, mctx, x_a, xq_a, prow);
       } else {
-        arwmh_transition64(p, U, dl, z, mu, pe, macc, lam, asc, updated, nacc, it, k0, k1, r, mctx, x_a, xq_a, prow,
-                           sg AMH_S64_SUB_ARG);
+        arwmh_transition64<kSG>(p, U, dl, z, mu, pe, macc, lam, asc, updated, nacc, it, k0, k1, r, mctx, x_a, xq_a,
+                                prow AMH_S64_SUB_ARG);
       }
       it += 1;
       if (p.col_z != nullptr || p.col_pe != nullptr) {
@@ -1116,11 +1150,11 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
 #endif
 }
 
-template <int WPB, bool kASSS = false>
+template <int WPB, bool kASSS = false, bool kSG = false>
 hipError_t launch_step64(const StepParams& p, hipStream_t s) {
   constexpr size_t shm = s64_lds_bytes<WPB>();
   static_assert(shm <= 163840, "d = 64 step kernel: LDS budget");
-  auto kern = arwmh_step64_kernel<WPB, kASSS>;
+  auto kern = arwmh_step64_kernel<WPB, kASSS, kSG>;
   int per_cu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, WPB * 64, shm);
   if (e != hipSuccess) return e;
@@ -1135,7 +1169,9 @@ hipError_t launch_step64(const StepParams& p, hipStream_t s) {
 }
 
 // ARWMH at the d = 64 Gaussian (amh_kernels.hip run_step)
-hipError_t run_step64(const StepParams& p, hipStream_t s) { return launch_step64<kS64Waves>(p, s); }
+hipError_t run_step64(const StepParams& p, hipStream_t s) {
+  return p.n_steps == 1 ? launch_step64<kS64Waves, false, true>(p, s) : launch_step64<kS64Waves>(p, s);
+}
 // ASSS at the d = 64 Gaussian (amh_asss.hip run_asss_step): the same kernel
 // around the ASSS transition.  16 waves (128 VGPRs, 64 B of spill) measured
 // 0.343 ms per sample() against 0.363 ms at 12 waves (170 VGPRs, no spill):
