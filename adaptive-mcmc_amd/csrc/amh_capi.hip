@@ -818,6 +818,119 @@ int amh_asss_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, in
 
 }  // extern "C"
 
+// ------------------------------------------- ASSS, the caller's potential --
+// amh_asss_ext.hip: the transition cut at every potential evaluation
+namespace {
+
+// every entry's checks of the handle, reported under its public name `who`
+int asss_ext_enter(amh_handle* h, const char* who) {
+  if (int rc = enter(h, who, false)) return rc;
+  if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, std::string(who) + ": needs AMH_MODEL_EXTERNAL");
+  if (h->cfg.dim > 64) return fail(h, AMH_EINVAL, std::string(who) + ": the external slice sampler needs d <= 64");
+  return AMH_OK;
+}
+
+amh::AsssExtParams asss_ext_params(const amh_handle* h, int64_t C, const amh_state& in, const amh_state& out,
+                                   const amh_collect* collect, const float* cand, const float* work,
+                                   int32_t* active) {
+  amh::AsssExtParams q{};
+  q.sp = step_params(h, C, in, out, 1, collect);
+  q.sp.accept_count = nullptr;
+  q.cand = const_cast<float*>(cand);
+  q.work = const_cast<float*>(work);
+  q.active = active;
+  return q;
+}
+
+int asss_ext_begin(amh_handle* h, amh::AsssExtParams& q, bool frozen, void* stream, const char* who) {
+  if (int rc = use_device(h, who)) return rc;
+  hipError_t e = hipMemsetAsync(q.active, 0, AMH_ASSS_EXT_ROUNDS * sizeof(int32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipMemsetAsync");
+  e = amh::run_asss_ext_begin(q, frozen, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amh_asss_ext_work_size(int32_t dim, int64_t* floats_per_chain) {
+  if (dim < 1 || dim > 64 || !floats_per_chain)
+    return fail(nullptr, AMH_EINVAL, "amh_asss_ext_work_size: dim must be in [1, 64]");
+  *floats_per_chain = amh::asss_ext_work_floats(dim);
+  return AMH_OK;
+}
+
+int amh_asss_ext_begin(amh_handle* h, int64_t num_chains, const amh_state* in, float* cand, float* work,
+                       int32_t* active, void* stream) {
+  if (int rc = asss_ext_enter(h, "amh_asss_ext_begin")) return rc;
+  if (!asss_state_ok(in) || !cand || !work || !active || num_chains < 1)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_begin: bad arguments");
+  amh::AsssExtParams q = asss_ext_params(h, num_chains, *in, *in, nullptr, cand, work, active);
+  return asss_ext_begin(h, q, false, stream, "amh_asss_ext_begin");
+}
+
+int amh_asss_ext_shrink(amh_handle* h, int64_t num_chains, const float* pe, int32_t round, float* cand, float* work,
+                        int32_t* active, void* stream) {
+  if (int rc = asss_ext_enter(h, "amh_asss_ext_shrink")) return rc;
+  if (!pe || !cand || !work || !active || num_chains < 1)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_shrink: bad arguments");
+  if (round < 0 || round >= AMH_ASSS_EXT_ROUNDS)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_shrink: round must be in [0, 50]");
+  if (int rc = use_device(h, "amh_asss_ext_shrink")) return rc;
+  amh::AsssExtParams q = asss_ext_params(h, num_chains, amh_state{}, amh_state{}, nullptr, cand, work, active);
+  q.pe = pe;
+  q.round = round;
+  const hipError_t e = amh::run_asss_ext_shrink(q, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_asss_ext_shrink");
+  return AMH_OK;
+}
+
+int amh_asss_ext_finish(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out,
+                        const float* cand, const float* work, const amh_collect* collect, void* stream) {
+  if (int rc = asss_ext_enter(h, "amh_asss_ext_finish")) return rc;
+  if (!asss_state_ok(in) || !asss_state_ok(out) || !cand || !work || num_chains < 1)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_finish: bad arguments");
+  if (collect && collect->thinning != 1) return fail(h, AMH_EINVAL, "amh_asss_ext_finish: thinning must be 1");
+  if (int rc = use_device(h, "amh_asss_ext_finish")) return rc;
+  const amh::AsssExtParams q = asss_ext_params(h, num_chains, *in, *out, collect, cand, work, nullptr);
+  const hipError_t e = amh::run_asss_ext_finish(q, false, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_asss_ext_finish");
+  return AMH_OK;
+}
+
+int amh_asss_ext_pnx_begin(amh_handle* h, const uint32_t key[2], const float* x_cur, int64_t num_chains,
+                           const float* loc, const float* scale_packed, int32_t t, float* cand, float* work,
+                           int32_t* active, void* stream) {
+  if (int rc = asss_ext_enter(h, "amh_asss_ext_pnx_begin")) return rc;
+  if (!key || !x_cur || !loc || !scale_packed || !cand || !work || !active || num_chains < 1 || t < 0)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_pnx_begin: bad arguments");
+  amh::AsssExtParams q = asss_ext_params(h, num_chains, amh_state{}, amh_state{}, nullptr, cand, work, active);
+  q.x_cur = const_cast<float*>(x_cur);
+  q.loc = loc;
+  q.scale = scale_packed;
+  q.key0 = key[0];
+  q.key1 = key[1];
+  q.t = t;
+  return asss_ext_begin(h, q, true, stream, "amh_asss_ext_pnx_begin");
+}
+
+int amh_asss_ext_pnx_finish(amh_handle* h, int64_t num_chains, const float* cand, const float* work, float* x_cur,
+                            void* stream) {
+  if (int rc = asss_ext_enter(h, "amh_asss_ext_pnx_finish")) return rc;
+  if (!cand || !work || !x_cur || num_chains < 1)
+    return fail(h, AMH_EINVAL, "amh_asss_ext_pnx_finish: bad arguments");
+  if (int rc = use_device(h, "amh_asss_ext_pnx_finish")) return rc;
+  amh::AsssExtParams q = asss_ext_params(h, num_chains, amh_state{}, amh_state{}, nullptr, cand, work, nullptr);
+  q.x_cur = x_cur;
+  const hipError_t e = amh::run_asss_ext_finish(q, true, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_asss_ext_pnx_finish");
+  return AMH_OK;
+}
+
+}  // extern "C"
+
 // -------------------------------------------------------------- evaluation --
 extern "C" {
 

@@ -252,6 +252,29 @@ hipError_t run_asss_step(int model_id, const StepParams& p, hipStream_t s);  // 
 hipError_t run_asss_step64(const StepParams& p, hipStream_t s);  // amh_step64.hip (d = 64 Gaussian)
 hipError_t run_step64(const StepParams& p, hipStream_t s);       // amh_step64.hip (ARWMH, d = 64 Gaussian: run_step)
 hipError_t run_asss_pnx(int model_id, const AsssPnxParams& p, hipStream_t s);
+// ASSS with the caller's potential (AMH_MODEL_EXTERNAL, d <= 64; amh_asss_ext.hip):
+// one transition as begin, shrink rounds 0 .. kAsssMaxIter around the caller's
+// U, finish.  A chain's record in the caller's workspace: S z [d], S v [d],
+// mu [d] and kAsssExtScalars scalar slots.
+constexpr int kAsssExtScalars = 20;
+constexpr int64_t asss_ext_work_floats(int d) { return 3 * (int64_t)d + kAsssExtScalars; }
+struct AsssExtParams {
+  StepParams sp;        // the states, C, d, the schedule and the finish pass's collection slot
+  float* cand;          // [2][C][d]: x(theta = 0), then the current candidate
+  float* work;          // [C][asss_ext_work_floats(d)]
+  int32_t* active;      // [kAsssMaxIter + 1]: chains that continued after each round
+  const float* pe;      // (shrink) [2][C]: the caller's U of cand
+  int32_t round;        // (shrink)
+  // sample_Pnx (frozen = true): the shared adapt state, the chains' points,
+  // the run's key and the transition number
+  const float *loc, *scale;
+  float* x_cur;
+  uint32_t key0, key1;
+  int32_t t;
+};
+hipError_t run_asss_ext_begin(const AsssExtParams& q, bool frozen, hipStream_t s);
+hipError_t run_asss_ext_shrink(const AsssExtParams& q, hipStream_t s);
+hipError_t run_asss_ext_finish(const AsssExtParams& q, bool frozen, hipStream_t s);
 // evaluation metrics (amh_eval.hip)
 int64_t kernel_sum_blocks(int64_t n, int64_t m);
 hipError_t run_kernel_sum(const float* A, int64_t n, const float* B, int64_t m, int d, float gamma, int skip_diag,

@@ -25,6 +25,7 @@ AMH_MODEL_MIXTURE = 6
 AMH_MODEL_EXTERNAL = 7  # the caller's potential (amh_propose / amh_step_external)
 AMH_STEP_PROPOSAL_READY = 1
 AMH_STEP_KEEP_PROPOSAL = 2
+AMH_ASSS_EXT_ROUNDS = 51  # shrink rounds 0 .. 50 of the external slice sampler (amh_asss_ext_shrink)
 
 
 class AmhConfig(ctypes.Structure):
@@ -76,6 +77,13 @@ def _signatures():
         # ASSS
         "amh_asss_step": (I, [P, I64, S, S, I32, COL, P]),
         "amh_asss_sample_pnx": (I, [P, KEY, P, I64, I64, P, P, I32, P, P]),
+        # ASSS, external potential (host-driven shrink loop)
+        "amh_asss_ext_work_size": (I, [I32, ctypes.POINTER(I64)]),
+        "amh_asss_ext_begin": (I, [P, I64, S, P, P, P, P]),
+        "amh_asss_ext_shrink": (I, [P, I64, P, I32, P, P, P, P]),
+        "amh_asss_ext_finish": (I, [P, I64, S, S, P, P, COL, P]),
+        "amh_asss_ext_pnx_begin": (I, [P, KEY, P, I64, P, P, I32, P, P, P, P]),
+        "amh_asss_ext_pnx_finish": (I, [P, I64, P, P, P, P]),
         # evaluation
         "amh_kernel_sum_scratch": (I64, [I64, I64]),
         "amh_kernel_sum": (I, [P, I64, P, I64, I32, F, I32, P, P, P]),

@@ -243,6 +243,74 @@ int amh_asss_sample_pnx(amh_handle* h, const uint32_t key[2], const float* x, in
                         int64_t n_samples, const float* loc, const float* scale_packed, int32_t n,
                         float* out, void* stream);
 
+/* ------------------------------------------ ASSS, the caller's potential ----
+ * AMH_MODEL_EXTERNAL (any other model: AMH_EINVAL), d <= 64: ASSS.sample
+ * (asss.py:197-251) with U evaluated by the caller.  The transition evaluates
+ * U only on its slice circle -- at theta = 0 (asss.py:216-217) and at every
+ * candidate of the shrinkage (asss.py:59-96) -- so it is cut there:
+ *   amh_asss_ext_begin    the draws at stream position in.i (asss.py:207,
+ *                         219, 225), y = S^-1 (x - mu) and its projection
+ *                         (asss.py:40-45, 214), the tangent (asss.py:219-222)
+ *                         and the circle through S; writes cand[0][c] =
+ *                         x(theta = 0), cand[1][c] = the first candidate
+ *                         x(theta_0) (cand: device [2][C][d]), every chain's
+ *                         record in work (device, C times
+ *                         amh_asss_ext_work_size floats) and zeroes active
+ *                         (device, AMH_ASSS_EXT_ROUNDS int32)
+ *   the caller            pe[0][c] = U(cand[0][c]), pe[1][c] = U(cand[1][c])
+ *                         (pe: device [2][C])
+ *   amh_asss_ext_shrink   round 0: the slice level t = (U(x(0)) + d log(1 -
+ *                         z_d)) - log u (asss.py:224-226) from pe[0], and the
+ *                         test of the first candidate (asss.py:72-76, NaN ->
+ *                         +inf).  A chain whose candidate is off the slice
+ *                         (and whose tangent is not degenerate) narrows its
+ *                         bracket (asss.py:78-92), draws Philox(round, i, 1),
+ *                         writes the next candidate over cand[1][c] and adds 1
+ *                         to active[round].
+ *   while active[round] > 0 (the caller reads it: one synchronisation per
+ *   round): round += 1, the caller's pe[1][c] = U(cand[1][c]) for every c,
+ *   amh_asss_ext_shrink(round).  Round r >= 1 tests candidate r with pe[1]
+ *   alone; round 50 stops every chain (asss.py:59 max_iterations), so
+ *   active[50] stays 0 and the loop ends after at most AMH_ASSS_EXT_ROUNDS
+ *   evaluations of cand[1].
+ *   amh_asss_ext_finish   the outcome (theta = 0 for a chain that hit the cap
+ *                         or whose tangent was degenerate, asss.py:94; its
+ *                         energy NaN -> +inf, asss.py:234), the adaptation
+ *                         (asss.py:237-251) and the state to `out` (may alias
+ *                         `in`); collect: z / potential_energy after the
+ *                         transition (thinning 1), as amh_step_external.
+ * A chain that has stopped is not touched by later rounds: cand[1][c] keeps
+ * its accepted point and the record keeps the pe[1][c] of the round that
+ * accepted it; what the caller returns for that row in later rounds is
+ * ignored, so a potential that is not bit-reproducible from call to call
+ * cannot change a stored energy.  Given the same U the bits are those of
+ * amh_asss_step with n_steps = 1.
+ * Contract: amh_asss_ext_finish takes the state amh_asss_ext_begin read,
+ * unmodified, with the cand / work that begin and the shrink rounds wrote for
+ * it (same num_chains).  Nothing is kept in the handle, so the library cannot
+ * check this; a caller that breaks it gets wrong numbers, not a fault (every
+ * index is formed from num_chains and d alone). */
+#define AMH_ASSS_EXT_ROUNDS 51
+int amh_asss_ext_work_size(int32_t dim, int64_t* floats_per_chain);
+int amh_asss_ext_begin(amh_handle* h, int64_t num_chains, const amh_state* in, float* cand, float* work,
+                       int32_t* active, void* stream);
+int amh_asss_ext_shrink(amh_handle* h, int64_t num_chains, const float* pe, int32_t round, float* cand, float* work,
+                        int32_t* active, void* stream);
+int amh_asss_ext_finish(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_state* out,
+                        const float* cand, const float* work, const amh_collect* collect, void* stream);
+/* ASSS.sample_Pnx (asss.py:271-303) likewise: transition t = 0 .. n-1 of every
+ * chain c (key split(key)[c], as amh_asss_sample_pnx; the draws at stream
+ * position t) from x_cur[c] (device [C][d]; the caller starts chain p *
+ * n_samples + s at x[p]) with the frozen shared (loc[d], scale_packed[P]):
+ * amh_asss_ext_pnx_begin, the rounds of amh_asss_ext_shrink as above, then
+ * amh_asss_ext_pnx_finish writes the outcome back to x_cur and nothing else.
+ * Same bits as amh_asss_sample_pnx given the same U. */
+int amh_asss_ext_pnx_begin(amh_handle* h, const uint32_t key[2], const float* x_cur, int64_t num_chains,
+                           const float* loc, const float* scale_packed, int32_t t, float* cand, float* work,
+                           int32_t* active, void* stream);
+int amh_asss_ext_pnx_finish(amh_handle* h, int64_t num_chains, const float* cand, const float* work, float* x_cur,
+                            void* stream);
+
 /* ----------------------------------------------------------- evaluation ----
  * python/utils/evaluation.py:223-294 (gaussian_kernel / mmd2_unbiased /
  * mmd_heuristic).  No handle: work goes to `stream` on the current device.
