@@ -1,8 +1,10 @@
 // amh_step64.hip -- the d = 64 persistent step kernel (arwmh_step64_kernel,
 // ARWMH and ASSS), the headline of bench.py.  In order: LDS layout and piece
 // table, the swap's group statements, batch readers / sweep 1 / scratch
-// writers, the pieces both transitions use (s64_matvec, s64_gauss_pot,
-// s64_rank_one_coef, s64_sweep2), asss_transition64 and arwmh_transition64,
+// writers, the row-replicated forms of a single-step launch (s64_rows,
+// s64_matvec_rows, s64_gauss_pot_rows), the pieces both transitions use
+// (s64_matvec, s64_gauss_pot, s64_rank_one_coef, s64_sweep2),
+// asss_transition64 and arwmh_transition64,
 // the kernel, its launcher and the entry points run_step64 / run_asss_step64.
 #include "amh_asss.h"
 #include "amh_device.h"
@@ -82,12 +84,17 @@ struct S64Sub {
 //   column.  Sweep 1, whose w_j is serial, uses v_readlane.  Sweep 2's four
 //   coefficients per column go through the scratch a quarter at a time into
 //   every row of 16 lanes and reach the FMAs as DPP row broadcasts
-//   (s64_rows_quarter, s64_sweep2_group).  A single-step ARWMH launch takes eta and diff through
-//   scalar registers instead (s64_lanes, s64_matvec_sg, s64_gauss_pot_sg): its
-//   compute phase runs beside the factor traffic and is bound by latency per
-//   wave, where an LDS round trip costs the launch 0.25 us and a batch of
-//   v_readlane has no wait.  A fused launch is bound by VALU issue and lost
-//   6 % with them; ASSS gained nothing.
+//   (s64_rows_quarter, s64_sweep2_group).
+// * Row-replicated registers, in a single-step ARWMH launch.  Its compute
+//   phase runs beside the factor traffic and is bound by latency per wave,
+//   where an LDS round trip costs the launch 0.25 us (0.68 us inside sweep 2's
+//   serial chain).  There eta, diff and sweep 2's four coefficient vectors are
+//   copied into every row of 16 lanes by permlane swaps (s64_rows: no scratch,
+//   no LDS, no wait) and every column's FMA takes its value as a DPP
+//   row_newbcast operand (s64_matvec_rows, s64_gauss_pot_rows,
+//   s64_sweep2<true>).  A fused launch is bound by VALU issue and lost 4 %
+//   with the proposal's rows form and 4 % with sweep 2's, ASSS 2 % with the
+//   proposal's: they keep the scratch forms.
 constexpr int kS64Waves = 16;
 // Cache policy of this kernel's factor traffic (its own: kLoadAux / kStoreAux
 // serve the other kernels), by the chain's place in the block's schedule
@@ -130,11 +137,9 @@ __device__ __forceinline__ void s64_store_policy(int cls, F&& f) {
     else f(integral_constant<int, kS64StoreAuxMid>{});
   }
 }
-constexpr int kS64EB = 8;   // proposal: broadcast columns per LDS wait / per batch of scalar registers
+constexpr int kS64EB = 8;   // proposal, vector from the scratch: broadcast columns per LDS wait
 constexpr int kS64PB = 8;   // potential, vector from the scratch: columns per LDS wait
-constexpr int kS64PG = 16;  // potential, vector in scalar registers: columns per LDS wait and per batch
 static_assert(kS64EB == 8 && kS64PB == 8, "the batch readers (lds_ld4x2w / lds_ld4x4w) read two quarter-vectors per stream");
-static_assert(kS64PG == 16, "s64_gauss_pot_sg waits for four quarter-rows; s64_lanes takes 8 or 16");
 typedef uint32_t uint32x4_t_ __attribute__((ext_vector_type(4)));
 constexpr int kS64P = 2080;                   // d(d+1)/2
 constexpr int kS64Z = 2080, kS64M = 2144, kS64S = 2208, kS64X = 2216;  // wave-buffer offsets (floats)
@@ -363,70 +368,103 @@ __device__ __forceinline__ float s64_keep_at(float old, float v) {
   return out;
 }
 
-// Lanes J0 .. J0 + N - 1 of v in scalar registers (v_readlane at immediate
-// lanes): how the proposal and the potential of a single-step ARWMH launch
-// broadcast their vector -- no scratch write, no broadcast LDS reads, no wait;
-// the FMAs take the scalar operand.  The batch's v_readlane stand together in
-// front of the pin and the
-// uses behind it, so a VALU read of an SGPR that v_readlane wrote (two wait
-// states, s64_sweep1x8) has them from the batch itself but possibly the first
-// use, which the compiler pads.  The values are bit copies: NaN payloads,
-// signed zeros and denormals arrive as they are.
-template <int J0, int N>
-__device__ __forceinline__ void s64_lanes(float v, float (&s)[N]) {
-  static_assert(N == 8 || N == 16, "batches of 8 or 16 lanes");
-  static_for<N>([&](auto K) { s[(int)K] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), J0 + K)); });
-  if constexpr (N == 8) {
-    asm volatile("" : "+s"(s[0]), "+s"(s[1]), "+s"(s[2]), "+s"(s[3]), "+s"(s[4]), "+s"(s[5]), "+s"(s[6]), "+s"(s[7]));
-  } else {
-    asm volatile("" : "+s"(s[0]), "+s"(s[1]), "+s"(s[2]), "+s"(s[3]), "+s"(s[4]), "+s"(s[5]), "+s"(s[6]), "+s"(s[7]),
-                 "+s"(s[8]), "+s"(s[9]), "+s"(s[10]), "+s"(s[11]), "+s"(s[12]), "+s"(s[13]), "+s"(s[14]), "+s"(s[15]));
-  }
+// v, one value per lane, copied into every row of 16 lanes: lane r of e[Q]
+// holds v of lane 16 Q + r mod 16.  permlane16_swap(v, v) gives rows 0 0 2 2
+// and rows 1 1 3 3, a permlane32_swap of each with itself the four quarters:
+// three swaps and three copies, no scratch, no LDS, no wait.  A column's FMA
+// then takes its value as a DPP row_newbcast operand (s64_dot16,
+// s64_sweep2_group) and needs no broadcast instruction.  Bit copies.
+__device__ __forceinline__ void s64_rows(float v, float (&e)[4]) {
+  const int iv = __float_as_int(v);
+  const auto a = __builtin_amdgcn_permlane16_swap(iv, iv, false, false);
+  const auto b = __builtin_amdgcn_permlane32_swap(a[0], a[0], false, false);
+  const auto c = __builtin_amdgcn_permlane32_swap(a[1], a[1], false, false);
+  e[0] = __int_as_float((int)b[0]);
+  e[1] = __int_as_float((int)c[0]);
+  e[2] = __int_as_float((int)b[1]);
+  e[3] = __int_as_float((int)c[1]);
 }
+// a[k & 3] = fma(e_k, x_k, a[k & 3]) for k = 0 .. 15, e_k the value of lane k of
+// this lane's row of 16 in e (one quarter of s64_rows), x(k) this lane's
+// factor: sixteen v_fmac_f32_dpp.  The s_nop 1 are the two wait states of a
+// DPP read of a VGPR that a VALU instruction (a swap's copy) may have written
+// right in front of the statement; inside it e is not written.
+#define AMH_ROW_FMAC(k, a) \
+  "v_fmac_f32_dpp %[a" #a "], %[e], %[x" #k "] row_newbcast:" #k " row_mask:0xf bank_mask:0xf\n\t"
+template <class X>
+__device__ __forceinline__ void s64_dot16(float (&a)[4], float e, X&& x) {
+  using std::integral_constant;
+#define AMH_ROW_X(k) [x##k] "v"(x(integral_constant<int, k>{}))
+  asm("s_nop 1\n\t" AMH_ROW_FMAC(0, 0) AMH_ROW_FMAC(1, 1) AMH_ROW_FMAC(2, 2) AMH_ROW_FMAC(3, 3) AMH_ROW_FMAC(4, 0)
+          AMH_ROW_FMAC(5, 1) AMH_ROW_FMAC(6, 2) AMH_ROW_FMAC(7, 3) AMH_ROW_FMAC(8, 0) AMH_ROW_FMAC(9, 1)
+              AMH_ROW_FMAC(10, 2) AMH_ROW_FMAC(11, 3) AMH_ROW_FMAC(12, 0) AMH_ROW_FMAC(13, 1) AMH_ROW_FMAC(14, 2)
+                  AMH_ROW_FMAC(15, 3)
+      : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3])
+      : [e] "v"(e), AMH_ROW_X(0), AMH_ROW_X(1), AMH_ROW_X(2), AMH_ROW_X(3), AMH_ROW_X(4), AMH_ROW_X(5), AMH_ROW_X(6),
+        AMH_ROW_X(7), AMH_ROW_X(8), AMH_ROW_X(9), AMH_ROW_X(10), AMH_ROW_X(11), AMH_ROW_X(12), AMH_ROW_X(13),
+        AMH_ROW_X(14), AMH_ROW_X(15));
+#undef AMH_ROW_X
+}
+#undef AMH_ROW_FMAC
+// ... for k = L0 .. L0 + 7 (L0 = 0 or 8): half a row
+#define AMH_ROW_FMAC(k, a) \
+  "v_fmac_f32_dpp %[a" #a "], %[e], %[x" #k "] row_newbcast:%[l" #k "] row_mask:0xf bank_mask:0xf\n\t"
+template <int L0, class X>
+__device__ __forceinline__ void s64_dot8(float (&a)[4], float e, X&& x) {
+  using std::integral_constant;
+  static_assert(L0 == 0 || L0 == 8, "k & 3 = (L0 + k) & 3");
+#define AMH_ROW_X(k) [x##k] "v"(x(integral_constant<int, k>{})), [l##k] "n"(L0 + k)
+  asm("s_nop 1\n\t" AMH_ROW_FMAC(0, 0) AMH_ROW_FMAC(1, 1) AMH_ROW_FMAC(2, 2) AMH_ROW_FMAC(3, 3) AMH_ROW_FMAC(4, 0)
+          AMH_ROW_FMAC(5, 1) AMH_ROW_FMAC(6, 2) AMH_ROW_FMAC(7, 3)
+      : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3])
+      : [e] "v"(e), AMH_ROW_X(0), AMH_ROW_X(1), AMH_ROW_X(2), AMH_ROW_X(3), AMH_ROW_X(4), AMH_ROW_X(5), AMH_ROW_X(6),
+        AMH_ROW_X(7));
+#undef AMH_ROW_X
+}
+#undef AMH_ROW_FMAC
 
-// U h, h one element per lane, kS64EB columns per batch of scalar registers.
-__device__ __forceinline__ float s64_matvec_sg(const float (&U)[64], float h) {
+// U h, h one element per lane: column j's h_j from the row-replicated
+// registers of h.  The accumulators and the final sum are s64_matvec's, the
+// products have their factors swapped: the same bits.
+__device__ __forceinline__ float s64_matvec_rows(const float (&U)[64], float h) {
+  float e[4];
+  s64_rows(h, e);
   float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  static_for<64 / kS64EB>([&](auto B) {
-    constexpr int b = B;
-    float e[kS64EB];
-    s64_lanes<kS64EB * b>(h, e);
-    static_for<kS64EB>([&](auto K) {
-      constexpr int j = kS64EB * b + K;
-      a4[j & 3] = fmaf(U[j], e[(int)K], a4[j & 3]);
-    });
+  static_for<4>([&](auto Q) {
+    s64_dot16(a4, e[(int)Q], [&](auto K) { return U[16 * (int)Q + (int)K]; });
     __builtin_amdgcn_sched_barrier(0);
   });
   return (a4[0] + a4[1]) + (a4[2] + a4[3]);
 }
 
 // The d = 64 Gaussian potential (GaussianM<64>::potential, the same float
-// operations and order): kS64PG columns of this lane's row of P per LDS wait,
-// diff_j in even-aligned scalar pairs for the packed FMAs, moved there while
-// the row's reads are in flight.
-__device__ __forceinline__ float s64_gauss_pot_sg(float diff, uint32_t prow, float c0) {
-  f32x2v y01 = {0.0f, 0.0f}, y23 = {0.0f, 0.0f};
-  static_for<64 / kS64PG>([&](auto B) {
-    constexpr int b = B;
-    constexpr int NQ = kS64PG / 4;
-    f32x4 pv[NQ];
-    static_for<NQ>([&](auto Q) { pv[(int)Q] = lds_ld4<16 * (NQ * b + Q)>(prow); });
-    float dv[kS64PG];
-    s64_lanes<kS64PG * b>(diff, dv);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]));
-    static_for<2 * NQ>([&](auto K2) {
-      const f32x4 q = pv[(int)K2 / 2];
-      const f32x2v pp = (K2 % 2 == 0) ? f32x2v{q[0], q[1]} : f32x2v{q[2], q[3]};
-      const f32x2v bp = {dv[2 * (int)K2], dv[2 * (int)K2 + 1]};
-      if constexpr (K2 % 2 == 0) {
-        y01 = __builtin_elementwise_fma(pp, bp, y01);
-      } else {
-        y23 = __builtin_elementwise_fma(pp, bp, y23);
-      }
-    });
+// operations and order) with diff_j from the row-replicated registers of diff.
+// This lane's row of P comes eight columns per LDS wait with the next eight in
+// flight behind them: each half of pv is read again as soon as its FMAs have
+// taken it (LDS returns in order: at most two reads outstanding means the
+// older two have landed).  The four accumulators are the packed form's
+// (column j adds to y[j & 3]), so the bits are s64_gauss_pot's.
+__device__ __forceinline__ float s64_gauss_pot_rows(float diff, uint32_t prow, float c0) {
+  f32x4 pv[4];
+  static_for<4>([&](auto Q) { pv[(int)Q] = lds_ld4<16 * (int)Q>(prow); });
+  float dq[4];
+  s64_rows(diff, dq);
+  float y4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  static_for<8>([&](auto B) {
+    constexpr int b = B, h = 2 * (b % 2);  // columns 8 b .. 8 b + 7 in pv[h], pv[h + 1]
+    if constexpr (b < 7) {
+      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(pv[h]), "+v"(pv[h + 1]));
+    } else {
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pv[h]), "+v"(pv[h + 1]));
+    }
+    s64_dot8<4 * h>(y4, dq[b / 2], [&](auto K) { return pv[h + (int)K / 4][(int)K % 4]; });
+    if constexpr (b + 2 < 8) {
+      pv[h] = lds_ld4<16 * (2 * (b + 2))>(prow);
+      pv[h + 1] = lds_ld4<16 * (2 * (b + 2) + 1)>(prow);
+    }
     __builtin_amdgcn_sched_barrier(0);
   });
-  const float y = (y01[0] + y01[1]) + (y23[0] + y23[1]);
+  const float y = (y4[0] + y4[1]) + (y4[2] + y4[3]);
   const float S = Grp<64>::sum(diff * y);
   return (0.5f * S) + c0;
 }
@@ -547,19 +585,28 @@ __device__ __forceinline__ void s64_sweep2_group(float (&U)[64], float& w, float
 // four columns, the coefficient vectors (this lane's ws, c, ac, bc) a quarter
 // at a time to every row through the quarter-vector scratch: four LDS round
 // trips per item and no broadcast read (the broadcast 16-B reads it replaces
-// took sixteen, and 64 ds_read_b128).  Returns the wave sum of the as_change
+// took sixteen, and 64 ds_read_b128).  kRows: all four quarters of the four
+// vectors by permlane swaps in front of the serial chain instead (s64_rows:
+// sixteen registers, no round trip).  Returns the wave sum of the as_change
 // terms (U_rj ac_j + bc_j w_r^{(j+1)})^2; ac and bc are where the transitions
 // differ.
+template <bool kRows>
 __device__ __forceinline__ float s64_sweep2(float (&U)[64], float delta, float ws, float c, float ac, float bc,
                                             uint32_t xq_a) {
   float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float w = delta;
-  float cw = 0.0f, cc = 0.0f, ca = 0.0f, cb = 0.0f;
+  float rw[4], rc[4], ra[4], rb[4];
+  if constexpr (kRows) {
+    s64_rows(ws, rw);
+    s64_rows(c, rc);
+    s64_rows(ac, ra);
+    s64_rows(bc, rb);
+  }
   static_for<16>([&](auto G4) {
-    constexpr int g = G4;
-    if constexpr (g % 4 == 0) s64_rows_quarter<g / 4>(xq_a, ws, c, ac, bc, cw, cc, ca, cb);
+    constexpr int g = G4, q = kRows ? g / 4 : 0;
     float t[4];
-    s64_sweep2_group<g>(U, w, t, cw, cc, ca, cb);
+    if constexpr (!kRows && g % 4 == 0) s64_rows_quarter<g / 4>(xq_a, ws, c, ac, bc, rw[0], rc[0], ra[0], rb[0]);
+    s64_sweep2_group<g>(U, w, t, rw[q], rc[q], ra[q], rb[q]);
     static_for<4>([&](auto Q) { s4[(int)Q] = fmaf(t[(int)Q], t[(int)Q], s4[(int)Q]); });
     column_fence<g, 2>();
   });
@@ -700,7 +747,7 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
   const S64Coef k = s64_rank_one_coef(ws, Dg, one, gamma, r);
   float sdiff = 0.0f;
   if (!k.revert) {
-    sdiff = sqrtf(s64_sweep2(U, delta, ws, k.c, k.q - dl, k.c * k.q, xq_a));
+    sdiff = sqrtf(s64_sweep2<false>(U, delta, ws, k.c, k.q - dl, k.c * k.q, xq_a));
     dl = k.q;
     updated = true;
   }
@@ -713,9 +760,9 @@ __device__ __forceinline__ void asss_transition64(const StepParams& p, float (&U
 // One ARWMH transition (arwmh.py:140-207) on the d = 64 persistent kernel's
 // registers: the same float operations in the same order as
 // arwmh_step_kernel<64, GaussianM, true> (oracle: orc_step), with the column
-// broadcasts read from the wave's LDS scratch or, sg (wave-uniform: a
-// single-step launch: its own instance of the kernel), the proposal's and the
-// potential's from scalar registers.
+// broadcasts read from the wave's LDS scratch or, sg (a single-step launch:
+// its own instance of the kernel), the proposal's, the potential's and
+// sweep 2's from row-replicated registers.
 template <bool sg>
 __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&U)[64], float& dl, float& z, float& mu,
                                                    float& pe, float& macc, float& lam, float& asc, bool& updated,
@@ -732,12 +779,12 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
   // ---- proposal z' = z + (L e^lam + eps I) xi  (arwmh.py:166-167), L xi = U (dl * xi)
   const float el = amh_expf(lam);
   const float eta = dl * xi;
-  const float acc = sg ? s64_matvec_sg(U, eta) : s64_matvec(U, eta, x_a, (uint32_t)r);
+  const float acc = sg ? s64_matvec_rows(U, eta) : s64_matvec(U, eta, x_a, (uint32_t)r);
   const float zp = z + fmaf(el, acc, p.eps * xi);
 
   AMH_S64_SUB(1)
-  // ---- potential (GaussianM<64>::potential with diff_j from the scratch or scalar registers), NaN -> +inf
-  float pep = sg ? s64_gauss_pot_sg(zp - mctx.mr, prow, mctx.c0)
+  // ---- potential (GaussianM<64>::potential with diff_j from the scratch or the rows of diff), NaN -> +inf
+  float pep = sg ? s64_gauss_pot_rows(zp - mctx.mr, prow, mctx.c0)
                  : s64_gauss_pot(zp - mctx.mr, x_a, prow, (uint32_t)r, mctx.c0);
   if (amh_isnan(pep)) pep = INFINITY;
   AMH_S64_SUB(2)
@@ -779,7 +826,7 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
     // sweep 2 with the as_change terms U_rj (q_j e1 - dl_j e0) + (c_j q_j e1) w_r^{(j+1)}
     const float ac = (k.q * e1) - (dl * el);
     const float bc = (k.c * k.q) * e1;
-    asc = sqrtf(s64_sweep2(U, delta, ws, k.c, ac, bc, xq_a));
+    asc = sqrtf(s64_sweep2<sg>(U, delta, ws, k.c, ac, bc, xq_a));
     dl = k.q;
     updated = true;
   } else {
@@ -807,12 +854,13 @@ __device__ __forceinline__ void arwmh_transition64(const StepParams& p, float (&
 // kASSS: the same persistent data movement around one ASSS transition
 // (asss_transition, amh_asss.h; asss.py:197-251) instead of the ARWMH one --
 // the state is the same but for mean_accept_prob / log_step_size (absent).
-// kSG: a single-step ARWMH launch (p.n_steps == 1, run_step64), whose proposal
-// and potential broadcast through scalar registers: an instance of its own, so
-// that neither instance carries the other's forms behind a branch.
+// kSG: a single-step ARWMH launch (p.n_steps == 1, run_step64), whose proposal,
+// potential and sweep 2 take their vectors from row-replicated registers: an
+// instance of its own, so that neither instance carries the other's forms
+// behind a branch.
 template <int WPB, bool kASSS = false, bool kSG = false>
 __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
-  static_assert(!(kASSS && kSG), "the scalar-register forms are ARWMH's");
+  static_assert(!(kASSS && kSG), "the row-replicated forms are the single-step ARWMH launch's");
   const StepParams& p_outer = p;
   constexpr int D = 64;
   constexpr uint32_t P = kS64P;
