@@ -67,6 +67,10 @@ struct amh_handle {
   const float* s64_scale = nullptr;  // d = 64 step kernel: the factor buffer its last launch wrote,
   int64_t s64_C = 0;                 // that launch's chain count
   int32_t s64_order = -1;            // and chain order (0 ascending, 1 descending; -1: no launch yet)
+  uint32_t* s64_heads = nullptr;     // d = 64 single-step launch: a head word per possible block (amh_s64_sched.h),
+                                     // allocated and zeroed once by amh_bind_model
+  int32_t s64_steal = (int32_t)amh::kS64StealDefault;  // its stealable-tail length (amh_step64_set_steal)
+  uint32_t s64_tag = 0;              // the last such launch's tag, 1 ... 65535 (0: none yet)
   std::string err;
 };
 
@@ -239,6 +243,28 @@ int32_t step64_chained(const amh_handle* h, const amh::StepParams& p) {
   return h->s64_order >= 0 && p.in.scale == h->s64_scale && p.C == h->s64_C;
 }
 
+static_assert(AMH_S64_STEAL_TRIES == amh::kS64StealTries, "include/amh.h states the victim count");
+constexpr size_t kS64HeadBytes =(size_t)amh::kS64HeadSlots * amh::kS64HeadStride * sizeof(uint32_t);
+
+// The head words, the tail length and the next tag of a single-step launch.
+// No launch and no memset of its own: every block re-arms its word, and
+// between launches every word is exhausted or carries another tag.  Only when
+// the 16-bit tag wraps are the words zeroed on the stream (tag 0 is never a
+// launch's), so that a word some launch of the last 65,535 left behind cannot
+// carry the new launch's tag.
+hipError_t step64_heads(amh_handle* h, amh::StepParams& p, hipStream_t s) {
+  if (!h->s64_heads || p.n_steps != 1) return hipSuccess;
+  if (++h->s64_tag > 0xFFFFu) {
+    const hipError_t e = hipMemsetAsync(h->s64_heads, 0, kS64HeadBytes, s);
+    if (e != hipSuccess) return e;
+    h->s64_tag = 1;
+  }
+  p.heads = h->s64_heads;
+  p.steal = h->s64_steal;
+  p.tag = (int32_t)h->s64_tag;
+  return hipSuccess;
+}
+
 void step64_launched(amh_handle* h, const amh::StepParams& p) {
   h->s64_scale = p.out.scale;
   h->s64_C = p.C;
@@ -370,6 +396,62 @@ int amh_step64_schedule(int32_t n, int32_t descending, int32_t* index, int32_t* 
   return AMH_OK;
 }
 
+int amh_step64_steal_schedule(int32_t n, int32_t descending, int32_t steal, int32_t block, int32_t grid,
+                              int32_t* n_own, int32_t* index, int32_t* cls, int32_t* victims, int32_t* n_victims) {
+  if (n < 0 || steal < 0 || grid < 1 || block < 0 || block >= grid || !n_own || !victims || !n_victims ||
+      (n > 0 && (!index || !cls)))
+    return fail(nullptr, AMH_EINVAL, "amh_step64_steal_schedule: bad arguments");
+  const amh::S64Sched s = amh::s64_sched((uint32_t)n, descending != 0, 1);
+  const uint32_t T = amh::s64_tail_len((uint32_t)n, (uint32_t)steal);
+  const uint32_t own = (uint32_t)n - T, lo = amh::s64_own_lo(T, descending != 0);
+  *n_own = (int32_t)own;
+  // the own part: what the LDS counter hands out, while it lies inside [lo, lo + own)
+  int32_t k = 0;
+  for (uint32_t v = amh::s64_draw(s, 0); v - lo < own; v = amh::s64_draw(s, (uint32_t)++k)) {
+    index[k] = (int32_t)v;
+    cls[k] = (int32_t)amh::s64_class(v, s.hot_lo, s.hot_n, s.tail_lo, s.tail_n);
+  }
+  if (k != (int32_t)own) return fail(nullptr, AMH_EINVAL, "amh_step64_steal_schedule: the own part is not a prefix");
+  // the tail: head counts 0 ... T - 1, as long as the word says they are valid
+  for (uint32_t c = 0; amh::s64_head_valid((1u << 16) | c, 1u, T); ++c, ++k) {
+    const uint32_t v = amh::s64_tail_index(s, (uint32_t)n, T, c);
+    index[k] = (int32_t)v;
+    cls[k] = (int32_t)amh::s64_class(v, s.hot_lo, s.hot_n, s.tail_lo, s.tail_n);
+  }
+  *n_victims = 0;
+  for (uint32_t t = 1; t <= amh::kS64StealTries; ++t) {
+    const uint32_t v = amh::s64_victim((uint32_t)block, (uint32_t)grid, t);
+    if (v == (uint32_t)grid) break;
+    victims[(*n_victims)++] = (int32_t)v;
+  }
+  return AMH_OK;
+}
+
+int amh_step64_set_steal(amh_handle* h, int32_t steal) {
+  if (int rc = enter(h, "amh_step64_set_steal", false)) return rc;
+  if (steal < 0 || steal > 0xFFFF) return fail(h, AMH_EINVAL, "amh_step64_set_steal: steal must be in [0, 65535]");
+  h->s64_steal = steal;
+  return AMH_OK;
+}
+
+int amh_step64_stolen(amh_handle* h, int64_t* stolen, void* stream) {
+  if (int rc = enter(h, "amh_step64_stolen", false)) return rc;
+  if (!stolen) return fail(h, AMH_EINVAL, "amh_step64_stolen: null argument");
+  *stolen = 0;
+  if (!h->s64_heads || h->s64_tag == 0) return AMH_OK;
+  if (int rc = use_device(h, "amh_step64_stolen")) return rc;
+  std::vector<uint32_t> w(kS64HeadBytes / sizeof(uint32_t));
+  hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemcpy(w.data(), h->s64_heads, kS64HeadBytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail(h, e, "amh_step64_stolen");
+  // a block's count is beside its head and was armed with the launch's tag
+  for (uint32_t b = 0; b < amh::kS64HeadSlots; ++b) {
+    const uint32_t c = w[(size_t)b * amh::kS64HeadStride + 1];
+    if ((c >> 16) == h->s64_tag) *stolen += (int64_t)(c & 0xFFFFu);
+  }
+  return AMH_OK;
+}
+
 int amh_destroy(amh_handle* h) {
   int rc = AMH_OK;
   if (h) {
@@ -381,6 +463,7 @@ int amh_destroy(amh_handle* h) {
     if (h->err_host && *(volatile int*)h->err_host != 0) rc = fail(nullptr, AMH_EHIP, kUpdateStuck);
     if (h->gamma_tab) (void)hipFree(h->gamma_tab);
     if (h->xpack) (void)hipFree(h->xpack);
+    if (h->s64_heads) (void)hipFree(h->s64_heads);
     for (amh::Scratch* s : {&h->partials, &h->split, &h->upd, &h->noise}) s->release();
     if (h->err_host) (void)hipHostFree(h->err_host);
   }
@@ -427,6 +510,16 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
         h->xpack = nullptr;
         return hip_fail(h, e, "amh_bind_model(diamonds tile copy)");
       }
+    }
+  }
+  if (model_id == AMH_MODEL_GAUSSIAN && dm == 64 && !h->s64_heads) {
+    // the d = 64 single-step launch's head words, zeroed once: tag 0 is no launch's
+    hipError_t e = hipMalloc(&h->s64_heads, kS64HeadBytes);
+    if (e == hipSuccess) e = hipMemset(h->s64_heads, 0, kS64HeadBytes);
+    if (e != hipSuccess) {
+      if (h->s64_heads) (void)hipFree(h->s64_heads);
+      h->s64_heads = nullptr;
+      return hip_fail(h, e, "amh_bind_model(d = 64 head words)");
     }
   }
   h->model_id = model_id;
@@ -541,6 +634,8 @@ int amh_step_chained(amh_handle* h, int64_t num_chains, const amh_state* in, con
   if (step64_shape(h)) {
     p.descending = step64_order(h, p);
     p.chained = step64_chained(h, p);
+    const hipError_t eh = step64_heads(h, p, s);
+    if (eh != hipSuccess) return hip_fail(h, eh, "amh_step(d = 64 head words)");
   }
   const hipError_t e = amh::run_step(h->model_id, p, s);
   if (e != hipSuccess) return hip_fail(h, e, "amh_step");

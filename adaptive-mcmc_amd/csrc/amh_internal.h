@@ -54,6 +54,10 @@ struct StepParams {
                            // uniform; the results do not depend on it, amh_capi.hip step64_order)
   int32_t chained;         // ... and its input is what the previous d = 64 launch wrote, in the opposite order:
                            // the launch has a hot part (amh_s64_sched.h)
+  uint32_t* heads;         // d = 64 single-step launch: the handle's head words (amh_s64_sched.h: kS64HeadSlots
+                           // lines of kS64HeadStride words), or null
+  int32_t steal;           // ... its stealable-tail length (0: no tail, the heads are not touched)
+  int32_t tag;             // ... and its 16-bit launch tag, 1 ... 65535
 };
 
 struct InitParams {

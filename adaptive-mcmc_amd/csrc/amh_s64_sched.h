@@ -61,4 +61,48 @@ __host__ __device__ inline uint32_t s64_class(uint32_t v, uint32_t hot_lo, uint3
   return (v - hot_lo < hot_n ? kS64Hot : 0u) | (v - tail_lo < tail_n ? kS64Tail : 0u);
 }
 
+// ---- stealable block tails (the single-step ARWMH launch) ----
+// The draw order above is split in two.  The first n - T draws, the own part,
+// come from the block's LDS counter.  The last T, the stealable tail, come from
+// the block's head word in global memory, which any block may draw from: a
+// block that has run out of work takes tail chains of blocks that are behind.
+// T = s64_tail_len(n, steal); steal = 0 is the schedule without a tail.  A head
+// word holds tag << 16 | count: the launch's 16-bit tag and the tail draws
+// handed out so far.  A draw is a returning add of 1; it is valid only if the
+// old value carries the launch's tag and a count below T (s64_head_valid).
+constexpr uint32_t kS64StealDefault = 16;    // the launch's default stealable-tail length
+constexpr uint32_t kS64StealTries = 4;       // victims a wave visits before it gives up
+constexpr uint32_t kS64StealStride = 8;      // victims b + 8, b + 16, ...: the same b % 8 (speed only)
+constexpr uint32_t kS64StealMax = 1u << 15;  // the count stays inside 16 bits whatever fails after the last draw
+constexpr uint32_t kS64HeadSlots = 1024;     // head words the handle owns: one per possible block
+constexpr uint32_t kS64HeadStride = 32;      // in words: every head on its own 128-B line, [head, stolen, pad]
+// at the headline shape (256 chains per block) the default tail lies inside the tail class
+static_assert(kS64StealDefault <= 256 * kS64HotNum / kS64HotDen && kS64StealDefault <= kS64StealMax,
+              "default stealable tail: every chain of it has class kS64Tail");
+
+__host__ __device__ constexpr uint32_t s64_tail_len(uint32_t n, uint32_t steal) {
+  const uint32_t t = steal < kS64StealMax ? steal : kS64StealMax;
+  return t < n ? t : n;
+}
+
+// local index of tail draw c (c < T): draw position n - T + c of the block's order
+__host__ __device__ inline uint32_t s64_tail_index(const S64Sched& s, uint32_t n, uint32_t T, uint32_t c) {
+  return s64_draw(s, n - T + c);
+}
+
+// The own part as a range of local indices [lo, lo + n - T): what the LDS
+// counter hands out is an own draw iff it lies inside.
+__host__ __device__ inline uint32_t s64_own_lo(uint32_t T, int descending) { return descending ? T : 0u; }
+
+// the k-th victim of block b in a grid of `grid` blocks, k = 1 ... kS64StealTries;
+// `grid` ("none") once the sequence would come back to b
+__host__ __device__ inline uint32_t s64_victim(uint32_t b, uint32_t grid, uint32_t k) {
+  const uint32_t v = (uint32_t)(((uint64_t)b + (uint64_t)kS64StealStride * k) % grid);
+  return v == b ? grid : v;
+}
+
+__host__ __device__ inline bool s64_head_valid(uint32_t old, uint32_t tag, uint32_t T) {
+  return (old >> 16) == tag && (old & 0xFFFFu) < T;
+}
+
 }  // namespace amh

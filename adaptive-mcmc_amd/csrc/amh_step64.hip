@@ -146,7 +146,7 @@ constexpr int kS64Z = 2080, kS64M = 2144, kS64S = 2208, kS64X = 2216;  // wave-b
 constexpr int kS64WB = kS64X + 64;            // floats per wave buffer (9,120 B): 64-float scratch
 constexpr int kS64Model = 64 * 68;            // GaussianM<64> rows (lds_bytes / 4)
 static_assert(kS64Z == 2080 && kS64S == kS64M + 64, "layout of prefetch_item<64>");
-// + 32 floats: the ticket, the hot / tail ranges after it (amh_s64_sched.h), and slack for flush_factor's 9 KiB read of the last wave buffer
+// + 32 floats: the ticket, the hot / tail ranges after it, the own part, n and T of a single-step launch (amh_s64_sched.h), and slack for flush_factor's 9 KiB read of the last wave buffer
 template <int WPB = kS64Waves>
 constexpr size_t s64_lds_bytes() { return ((size_t)kS64Model + (size_t)WPB * kS64WB + 32) * sizeof(float); }
 
@@ -869,6 +869,18 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   using Gp = Grp<64>;
   using M = GaussianM<64>;
   extern __shared__ float lds[];
+  // kSG with a stealable tail: the block re-arms its head word (and its count
+  // of stolen chains beside it) to tag << 16.  The exchanges return nothing;
+  // the wait for them stands in front of the barrier below, behind the model's
+  // staging, so that no wave of the block draws from the head before it.
+  if constexpr (kSG) {
+    if (threadIdx.x == 0 && p.steal > 0) {
+      uint32_t* head = p.heads + (size_t)blockIdx.x * kS64HeadStride;
+      const uint32_t armed = (uint32_t)p.tag << 16;
+      (void)__hip_atomic_exchange(head, armed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_exchange(head + 1, armed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
   M::stage(lds, p.model, D);
   float* tick = lds + kS64Model + WPB * kS64WB;
   // The block's ticket counter hands out the block-local chain index: 0, 1,
@@ -888,6 +900,14 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     tick[5] = __uint_as_float(sch.hot_n);
     tick[6] = __uint_as_float(sch.tail_lo);
     tick[7] = __uint_as_float(sch.tail_n);
+    if constexpr (kSG) {  // the own part (amh_s64_sched.h), the block's chain count and its tail length
+      const uint32_t n = (uint32_t)(blk_hi - blk_lo), T = s64_tail_len(n, (uint32_t)p.steal);
+      tick[8] = __uint_as_float(s64_own_lo(T, p.descending));
+      tick[9] = __uint_as_float(n - T);
+      tick[10] = __uint_as_float(n);
+      tick[11] = __uint_as_float(T);
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the head is re-armed
+    }
   }
   __syncthreads();
   const auto mctx = M::prepare(p.model, D, lane_id());
@@ -922,8 +942,66 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
   // readfirstlane): bits 30-31 of the word carry the class, a "no chain" value
   // is clamped below them and stays >= n.  The result is the global chain index
   // with the class at kS64TagShift; kEnd and -1 carry no class.
+  // kSG: a draw from the head word of block vb, whose n chains start at lo
+  // (amh_s64_sched.h).  The ticket is the add's own return value and the chain
+  // it names was written by an earlier launch: no fence.  Everything comes from
+  // the kernarg segment and dies here; -1 when the head is exhausted, was armed
+  // by another launch or is not armed yet.
+  auto head_draw = [&](const StepParams& q, uint32_t vb, int64_t lo, uint32_t n) -> int64_t {
+    const uint32_t T = s64_tail_len(n, (uint32_t)q.steal);
+    uint32_t old = 0;
+    if (lane_id() == 0)
+      old = __hip_atomic_fetch_add(q.heads + (size_t)vb * kS64HeadStride, 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
+    if (!s64_head_valid(old, (uint32_t)q.tag, T)) return -1;
+    const S64Sched s = s64_sched(n, q.descending, q.chained);
+    const uint32_t v = s64_tail_index(s, n, T, old & 0xFFFFu);
+    const uint32_t cls = s64_class(v, s.hot_lo, s.hot_n, s.tail_lo, s.tail_n);
+    return (lo + (int64_t)v) | ((int64_t)cls << kS64TagShift);
+  };
+  // kSG, the LDS counter is spent: the own head, then the heads of blocks
+  // b + 8, b + 16, ... (mod the grid), at most kS64StealTries of them.  A wave
+  // gets "no item" (-1) only after a failing draw on its own head, and draws no
+  // more after that, so a head is exhausted when its block has ended.
+  auto tail_ticket = [&]() -> int64_t {
+    const StepParams& q = reload_kernarg(p_outer);
+    if (q.steal <= 0) return -1;
+    uint32_t nn = 0;
+    if (lane_id() == 0) {
+      asm volatile("ds_read_b32 %0, %1 offset:40\n\ts_waitcnt lgkmcnt(0)" : "=&v"(nn) : "v"(tk_addr) : "memory");
+    }
+    nn = (uint32_t)__builtin_amdgcn_readfirstlane((int)nn);
+    const uint32_t b = blockIdx.x, grid = gridDim.x;
+    int64_t t = head_draw(q, b, blk_lo, nn);
+    for (uint32_t k = 1; t < 0 && k <= kS64StealTries; ++k) {
+      const uint32_t vb = s64_victim(b, grid, k);
+      if (vb == grid) break;
+      const int64_t lo = q.C * (int64_t)vb / grid, hi = q.C * ((int64_t)vb + 1) / grid;
+      t = head_draw(q, vb, lo, (uint32_t)(hi - lo));
+      if (t >= 0 && lane_id() == 0)  // for amh_step64_stolen: this block took a chain of another's
+        (void)__hip_atomic_fetch_add(q.heads + (size_t)b * kS64HeadStride + 1, 1u, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return t;
+  };
   auto ticket = [&]() -> int64_t {
     uint32_t v = 0;
+    if constexpr (kSG) {
+      // the own part from the LDS counter; a value outside it sends the wave to the heads
+      if (lane_id() == 0) {
+        uint32x4_t_ b;
+        uint32_t o_lo, o_n;
+        asm volatile("ds_add_rtn_u32 %0, %4, %5\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b32 %2, %4 offset:32\n\t"
+                     "ds_read_b32 %3, %4 offset:36\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(v), "=&v"(b), "=&v"(o_lo), "=&v"(o_n) : "v"(tk_addr), "v"(tk_step) : "memory");
+        const uint32_t cls = s64_class(v, b[0], b[1], b[2], b[3]);
+        v = (v - o_lo < o_n) ? (v | (cls << 30)) : ~0u;
+      }
+      const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+      if (w == ~0u) return tail_ticket();
+      return (blk_lo + (int64_t)(w & 0x3FFFFFFFu)) | ((int64_t)(w >> 30) << kS64TagShift);
+    }
     if (lane_id() == 0) {
       uint32x4_t_ b;
       asm volatile("ds_add_rtn_u32 %0, %2, %3\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
@@ -935,6 +1013,11 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     return (blk_lo + (int64_t)(w & 0x3FFFFFFFu)) | ((int64_t)(w >> 30) << kS64TagShift);
   };
   auto ix = [](int64_t t) -> int64_t { return t & kS64IdxMask; };
+  // is t a chain?  kSG: a ticket may name any block's chain, "no item" is -1
+  auto valid = [&](int64_t t) -> bool {
+    if constexpr (kSG) return t >= 0;
+    else return ix(t) < kEnd;
+  };
   // the DMA of a drawn chain, at its class's load policy
   auto prefetch = [&](int64_t t, int ln) {
     s64_load_policy(s64_cls(t), [&](auto AUX) { prefetch_item<64, false, decltype(AUX)::value>(p, ix(t), D, wb, ln); });
@@ -998,10 +1081,16 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     s64_store_policy(s64_cls(t), [&](auto AUX) { flush_aux(ix(t), AUX); });
   };
 
+  // The fused and the ASSS instance draw two items ahead (nxt2 below).  kSG
+  // draws one ahead, at the top of the hand-over whose DMA the draw feeds: the
+  // waves of a block that is behind then hold no reserved chains, which other
+  // blocks can take from its head instead, and the draw is not live across the
+  // loop.
   int64_t item = ticket();
-  int64_t nxt = ix(item) < kEnd ? ticket() : kEnd;
-  if (ix(item) < kEnd) prefetch(item, lane_id());
-  for (; ix(item) < kEnd;) {
+  int64_t nxt = kEnd;
+  if constexpr (!kSG) nxt = valid(item) ? ticket() : kEnd;
+  if (valid(item)) prefetch(item, lane_id());
+  for (; valid(item);) {
     int lane = lane_id();
     asm volatile("" : "+v"(lane));
     const int r = lane;
@@ -1014,6 +1103,9 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     // wave priority so the memory queue is re-armed before other waves'
     // compute: 239 -> 236 us per launch (tools/gpu_prio.sh A/B)
     __builtin_amdgcn_s_setprio(3);
+    // kSG: nothing is outstanding on vector memory here, so a draw from a head
+    // word (a global round trip, tail chains only) waits for itself alone
+    if constexpr (kSG) nxt = ticket();
     // ---- item k-1's z / loc / scalars leave from registers
     if (prev >= 0) store_small(ix(prev), r);
     const bool wr = prev >= 0 && prev_upd;
@@ -1056,7 +1148,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     //      piece of item k+1 is issued into the addresses just read.  The wait
     //      at the top of the loop stays the only one on vector memory: every
     //      LDS access from here to there is inline asm.
-    const bool have_nxt = ix(nxt) < kEnd;
+    const bool have_nxt = valid(nxt);
     const Buf Lnx(uniform_ptr(p.in.scale + ix(nxt) * P), P * 4u);  // (unused without a next item)
     auto piece_in = [&](auto M) {  // DMA of piece M of item k+1, at its class's load policy
       constexpr int m = M;
@@ -1130,7 +1222,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     int64_t nxt2 = kEnd;
     if (have_nxt) {
       prefetch_item_small<64, false>(p, ix(nxt), D, wb, lane);
-      nxt2 = ticket();
+      if constexpr (!kSG) nxt2 = ticket();
     }
     __builtin_amdgcn_s_setprio(0);
     AMH_S64_PHASE(2)  // (c) -> last DMA issued
@@ -1156,7 +1248,7 @@ __global__ __launch_bounds__(WPB * 64) void arwmh_step64_kernel(StepParams p) {
     prev = item;
     prev_upd = Gp::any(updated);
     item = nxt;
-    nxt = nxt2;
+    if constexpr (!kSG) nxt = nxt2;
     AMH_S64_PHASE(3)  // (d) compute
 #ifdef AMH_STAMPS
     ++st_items;
@@ -1212,6 +1304,15 @@ hipError_t launch_step64(const StepParams& p, hipStream_t s) {
   int64_t blocks = (int64_t)cus * per_cu;
   if (blocks > need) blocks = need;
   if (blocks < 1) blocks = 1;
+  if constexpr (kSG) {
+    // a stealable tail needs a head word per block and a tag (amh_capi.hip); without them no tail
+    if (p.heads == nullptr || blocks > (int64_t)kS64HeadSlots || p.tag < 1 || p.tag > 0xFFFF || p.steal < 0) {
+      StepParams q = p;
+      q.steal = 0;
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WPB * 64), shm, s, q);
+      return hipGetLastError();
+    }
+  }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WPB * 64), shm, s, p);
   return hipGetLastError();
 }

@@ -62,6 +62,9 @@ def _signatures():
         "amh_check_device": (I, [P]),
         "amh_step_order": (I, [P, ctypes.POINTER(I32)]),
         "amh_step64_schedule": (I, [I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "amh_step64_steal_schedule": (I, [I32, I32, I32, I32, I32] + [ctypes.POINTER(I32)] * 5),
+        "amh_step64_set_steal": (I, [P, I32]),
+        "amh_step64_stolen": (I, [P, ctypes.POINTER(I64), P]),
         "amh_bind_model": (I, [P, I32, P, I64, ctypes.POINTER(I64), I32]),
         "amh_init": (I, [P, KEY, I64, I64, P, S, P]),
         "amh_step": (I, [P, I64, S, S, I32, COL, P]),
@@ -204,6 +207,17 @@ class Handle:
         order = ctypes.c_int32(-2)
         check(self._lib.amh_step_order(self.h, ctypes.byref(order)), self.h)
         return order.value
+
+    def set_steal(self, steal: int):
+        """Stealable-tail length of the single-step d = 64 launches (0: none); changes no result."""
+        check(self._lib.amh_step64_set_steal(self.h, int(steal)), self.h)
+
+    def stolen(self) -> int:
+        """Chains of the last single-step d = 64 launch that a block took from another block's tail."""
+        n = ctypes.c_int64(-1)
+        with torch.cuda.device(self.device):
+            check(self._lib.amh_step64_stolen(self.h, ctypes.byref(n), stream_ptr(self.device)), self.h)
+        return n.value
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

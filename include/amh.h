@@ -147,6 +147,32 @@ int amh_step_order(amh_handle* h, int32_t* order);
  * counterpart in the reference. */
 int amh_step64_schedule(int32_t n, int32_t descending, int32_t* index, int32_t* cls);
 
+/* The same schedule with a stealable tail of `steal` chains, as a single-step
+ * d = 64 launch (amh_step with n_steps = 1) runs it (host only).  The draw
+ * order is that of amh_step64_schedule; its first *n_own = n - T draws, T =
+ * min(n, steal, 32768), come from the block's own counter, the last T from the
+ * block's head word in device memory, from which blocks that have run out of
+ * work may draw too.  index and cls hold n entries, the own part first.
+ * victims receives the blocks whose head words block `block` of a grid of
+ * `grid` visits, in order, once its own is exhausted: at most
+ * AMH_S64_STEAL_TRIES entries, *n_victims of them, never `block` itself.  No
+ * counterpart in the reference. */
+#define AMH_S64_STEAL_TRIES 4
+int amh_step64_steal_schedule(int32_t n, int32_t descending, int32_t steal, int32_t block, int32_t grid,
+                              int32_t* n_own, int32_t* index, int32_t* cls, int32_t* victims, int32_t* n_victims);
+
+/* The stealable-tail length of the handle's single-step d = 64 launches, 0 ...
+ * 65535: 0 is the schedule without a tail (no block takes another's chains).
+ * It changes which block computes a chain and no result.  A handle's launches
+ * must be ordered on the device (one stream, or streams ordered by events): the
+ * head words are the handle's.  No counterpart in the reference. */
+int amh_step64_set_steal(amh_handle* h, int32_t steal);
+
+/* *stolen = the chains of the handle's last single-step d = 64 launch that a
+ * block took from another block's tail.  Synchronises `stream`, on which that
+ * launch was enqueued.  A measurement aid. */
+int amh_step64_stolen(amh_handle* h, int64_t* stolen, void* stream);
+
 /* Model plug-in (arwmh.py:109-116 / the scripts' numpyro models).
  * data: device pointer, n_data floats; iparams model-specific:
  *   GAUSSIAN: none.  EIGHT_SCHOOLS: {J}.  KIDIQ: {N}.  DIAMONDS: {N, K}. */
