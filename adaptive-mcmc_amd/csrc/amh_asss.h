@@ -10,6 +10,15 @@ namespace amh {
 
 constexpr int kAsssMaxIter = 50;  // asss.py:59 max_iterations
 
+// The scalar slots of a chain's record in the transition cut around a caller's
+// potential (after S z, S v and mu; asss_ext_work_floats): written by the begin
+// kernels of amh_asss_ext.hip and amh_pooled_asss_ext.hip, advanced by
+// asss_ext_shrink_kernel, read by the finish kernels.
+enum : int {
+  kZd, kVd, kTh, kThmin, kThmax, kIter, kUt, kOm0, kOm, kDegen, kCont, kTpe, kU0, kUx, kIt, kKey0, kKey1, kNumScalars
+};
+static_assert(kNumScalars <= kAsssExtScalars, "record too small");
+
 // The pieces of one transition (asss.py:197-251), each written once: the fused
 // transition below runs them back to back with the model's potential inside;
 // the external-potential kernels (amh_asss_ext.hip) run the same pieces cut at

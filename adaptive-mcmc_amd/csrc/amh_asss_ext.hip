@@ -27,17 +27,13 @@
 // later evaluations of that row (every round evaluates all rows) are ignored.
 //
 // The record of chain c is asss_ext_work_floats(d) floats at work + c * that:
-// S z [d], S v [d], mu [d], then the scalars below.
+// S z [d], S v [d], mu [d], then the scalars kZd .. kKey1 of amh_asss.h (the
+// pooled begin kernel of amh_pooled_asss_ext.hip writes the same record).
 #include "amh_asss.h"
 
 namespace amh {
 
 namespace {
-
-enum : int {
-  kZd, kVd, kTh, kThmin, kThmax, kIter, kUt, kOm0, kOm, kDegen, kCont, kTpe, kU0, kUx, kIt, kKey0, kKey1, kNumScalars
-};
-static_assert(kNumScalars <= kAsssExtScalars, "record too small");
 
 template <int G>
 __device__ __forceinline__ int64_t wave_items(int64_t C, int64_t& wave0, int64_t& wstride) {

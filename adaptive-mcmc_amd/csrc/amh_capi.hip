@@ -1607,9 +1607,63 @@ int pooled_asss_update_impl(amh_handle* h, const double* sums, const amh_pooled_
   return AMH_OK;
 }
 
+// ... and the checks of the entries around a caller's potential
+int pooled_asss_ext_enter(amh_handle* h, const char* who) {
+  if (int rc = enter(h, who, false)) return rc;
+  if (h->model_id != AMH_MODEL_EXTERNAL) return fail(h, AMH_EINVAL, std::string(who) + ": needs AMH_MODEL_EXTERNAL");
+  if (h->cfg.dim > 64) return fail(h, AMH_EINVAL, std::string(who) + ": dim must be <= 64");
+  return AMH_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int amh_pooled_asss_ext_begin(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, float* cand,
+                              float* work, int32_t* active, void* stream) {
+  const char* const who = "amh_pooled_asss_ext_begin";
+  if (int rc = pooled_asss_ext_enter(h, who)) return rc;
+  amh::PooledAsssExtParams q{};
+  if (int rc = pooled_ext_params(h, num_chains, in, t, who, &q.sp)) return rc;
+  if (!cand || !work || !active) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  q.cand = cand;
+  q.work = work;
+  hipError_t e = hipMemsetAsync(active, 0, AMH_ASSS_EXT_ROUNDS * sizeof(int32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, std::string(who) + "/hipMemsetAsync");
+  e = amh::run_pooled_asss_ext_begin(q, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+int amh_pooled_asss_ext_finish(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, const float* cand,
+                               const float* work, float* z_out, float* pe_out, double* sums, int32_t accumulate,
+                               void* stream) {
+  const char* const who = "amh_pooled_asss_ext_finish";
+  if (int rc = pooled_asss_ext_enter(h, who)) return rc;
+  amh::PooledAsssExtParams q{};
+  if (int rc = pooled_ext_params(h, num_chains, in, 0, who, &q.sp)) return rc;
+  if (!cand || !work || !z_out || !pe_out || !sums) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = use_device(h, who)) return rc;
+  const int64_t chunk = (int64_t)amh::kPoolWaves * q.sp.cpw;
+  const int64_t n_chunks = (num_chains + chunk - 1) / chunk;
+  if (int rc = reserve_partials(h, n_chunks, false, stream, who)) return rc;
+  q.cand = const_cast<float*>(cand);
+  q.work = const_cast<float*>(work);
+  q.sp.z_out = z_out;
+  q.sp.pe_out = pe_out;
+  q.sp.partials = h->partials.as<double>();
+  const hipError_t e = amh::run_pooled_asss_ext_finish(q, sums, accumulate != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(h, e, who);
+  return AMH_OK;
+}
+
+int amh_pooled_asss_ext_update(amh_handle* h, const double* sums, const amh_pooled_state* in,
+                               const amh_pooled_state* out, int32_t k_steps, void* stream) {
+  const char* const who = "amh_pooled_asss_ext_update";
+  if (int rc = pooled_asss_ext_enter(h, who)) return rc;
+  return pooled_asss_update_impl(h, sums, in, out, k_steps, stream, who);
+}
 
 int amh_pooled_asss_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
                             float* z_out, float* pe_out, double* sums, void* stream) {

@@ -279,6 +279,17 @@ struct AsssExtParams {
 hipError_t run_asss_ext_begin(const AsssExtParams& q, bool frozen, hipStream_t s);
 hipError_t run_asss_ext_shrink(const AsssExtParams& q, hipStream_t s);
 hipError_t run_asss_ext_finish(const AsssExtParams& q, bool frozen, hipStream_t s);
+// Pooled ASSS with the caller's potential (d <= 64; amh_pooled_asss_ext.hip):
+// transition t of a block as begin, the shrink rounds of run_asss_ext_shrink on
+// the same record layout, finish (the outcome and the transition's sums,
+// `accumulate`: added to the block's)
+struct PooledAsssExtParams {
+  PooledExtParams sp;  // the shared state, the chains, t; the finish pass's z_out / pe_out / partials / cpw
+  float* cand;         // [2][C][d]: x(theta = 0), then the current candidate
+  float* work;         // [C][asss_ext_work_floats(d)]
+};
+hipError_t run_pooled_asss_ext_begin(const PooledAsssExtParams& q, hipStream_t s);
+hipError_t run_pooled_asss_ext_finish(const PooledAsssExtParams& q, double* sums, int accumulate, hipStream_t s);
 // evaluation metrics (amh_eval.hip)
 int64_t kernel_sum_blocks(int64_t n, int64_t m);
 hipError_t run_kernel_sum(const float* A, int64_t n, const float* B, int64_t m, int d, float gamma, int skip_diag,

@@ -11,24 +11,12 @@
 //
 // Noise: the per-chain ASSS stream of amh_asss.h at position i + t with the
 // chain's key (oracle/asss_np.draws).
-#include "amh_asss.h"
 #include "amh_device.h"
-#include "amh_pooled_device.h"
+#include "amh_pooled_asss.h"
 
 namespace amh {
 
 namespace {
-
-// The frozen shared state as one lane sees it: S = (L + eps I) sqrt(d) with
-// row r of L in LDS at prow (asss.py:213).
-struct SharedRow {
-  uint32_t prow;  // LDS address of row r of the staged factor (row 0 in lanes r >= d)
-  float mu;       // mu_r
-  float invD;     // 1 / S_rr
-  float sd;       // sqrt(d)
-  float epsd;     // eps sqrt(d)
-  float eps;
-};
 
 // One ASSS transition (asss.py:210-244) of the wave's chain at stream position
 // `it` against the shared state; x / pe are replaced by x' / pe'.  Returns
@@ -50,36 +38,9 @@ __device__ __forceinline__ bool pooled_asss_transition(const SharedRow& sh, floa
   const float ut = amh_unif01_from_bits(Gp::template bcast_u<0>(o.v[2]));
   const float th0 = 6.28318548f * amh_unif01_from_bits(Gp::template bcast_u<0>(o.v[3]));
 
-  // ---- y = S^-1 (x - mu): forward substitution, a column sweep over the LDS
-  // rows (zero above the diagonal: lanes r <= j are left alone, lane j's own
-  // b is spent once y_j is taken)
-  float b = act ? x - mu : 0.0f;
-  float y = 0.0f;
-  static_for<4>([&](auto B) {
-    constexpr int bq = B;
-    if (16 * bq < d) {
-      f32x4 pv[4];
-      static_for<4>([&](auto Q) {
-        pv[Q] = (4 * (4 * bq + Q) < d) ? lds_ld4<16 * (4 * bq + Q)>(sh.prow) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      });
-      lds_wait(pv[0], pv[1], pv[2], pv[3]);
-      static_for<16>([&](auto Q) {
-        constexpr int j = 16 * bq + Q;
-        if (j < d) {
-          const float yj = Gp::template bcast<j>(b * sh.invD);
-          y = capture<G, j>(y, yj, r);
-          b = fmaf(-pv[Q / 4][Q % 4], yj * sh.sd, b);
-        }
-      });
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-
-  // ---- stereographic projection (asss.py:40-45)
-  const float ns = Gp::sum(act ? y * y : 0.0f);
-  const float den = ns + 1.0f;
-  const float zr = act ? (2.0f * y) / den : 0.0f;
-  const float zd = (ns - 1.0f) / den;
+  // ---- y = S^-1 (x - mu) and its stereographic projection (asss.py:40-45)
+  float zr, zd;
+  pooled_asss_project(sh, x, d, r, act, zr, zd);
 
   // ---- v orthogonal to z on S^d (asss.py:219-222), projected with fmaf and
   // with the degenerate tangent's fallback theta = 0, as amh_asss.h
@@ -92,8 +53,8 @@ __device__ __forceinline__ bool pooled_asss_transition(const SharedRow& sh, floa
   vd = degen ? 0.0f : vd / nv;
 
   // ---- S z_1d and S v_1d (asss.py:48-56 for both circle directions)
-  const float Sz = lds_row_dot64(sh.prow, d, sh.sd * zr, act) + sh.epsd * zr;
-  const float Sv = lds_row_dot64(sh.prow, d, sh.sd * v, act) + sh.epsd * v;
+  float Sz, Sv;
+  pooled_asss_circle(sh, zr, v, d, act, Sz, Sv);
 
   // x on the circle at angle (c, s); om = 1 - z_d(th)
   auto x_at = [&](float c, float s, float& om) -> float {
@@ -174,13 +135,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_asss_stats_kernel(Pool
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
   const auto mctx = M<G>::prepare(p.model, d, r);
   const int32_t it = __builtin_amdgcn_readfirstlane(p.i[0]);
-  SharedRow sh;
-  sh.sd = sqrtf((float)d);
-  sh.eps = p.eps;
-  sh.epsd = p.eps * sh.sd;
-  sh.mu = act ? p.mu[r] : 0.0f;
-  sh.prow = lds_addr(lrow + (act ? r : 0) * ld);
-  sh.invD = act ? 1.0f / ((lrow[r * ld + r] + p.eps) * sh.sd) : 0.0f;
+  const SharedRow sh = pooled_asss_shared_row(lrow, p.mu, p.eps, d, r, act);
 
   const int cpw = p.cpw;
   const int64_t chunk0 = (int64_t)blockIdx.x * kPoolWaves * cpw;

@@ -108,6 +108,10 @@ def _signatures():
         "amh_pooled_asss_stats_k": (I, [P, I64, PS, I32, P, P, P, P]),
         "amh_pooled_asss_update_k": (I, [P, P, PS, PS, I32, P]),
         "amh_pooled_asss_step_k": (I, [P, I64, PS, PS, I32, I32, P, P]),
+        # pooled ASSS, external potential (the shrink rounds are amh_asss_ext_shrink)
+        "amh_pooled_asss_ext_begin": (I, [P, I64, PS, I32, P, P, P, P]),
+        "amh_pooled_asss_ext_finish": (I, [P, I64, PS, P, P, P, P, P, I32, P]),
+        "amh_pooled_asss_ext_update": (I, [P, P, PS, PS, I32, P]),
         # pooled covariance, exact sums
         "amh_pooled_exact_size": (I, [I32, ctypes.POINTER(I64)]),
         "amh_pooled_chunk_chains": (I, [I32, I64, ctypes.POINTER(I64)]),

@@ -505,6 +505,46 @@ int amh_pooled_asss_step_k(amh_handle* h, int64_t num_chains, const amh_pooled_s
                            const amh_pooled_state* out, int32_t n_steps, int32_t sync_every, double* sums,
                            void* stream);
 
+/* Pooled ASSS with the caller's potential (AMH_MODEL_EXTERNAL, d <= 64): the
+ * transition above cut at every potential evaluation, as amh_asss_ext_* cut
+ * the per-chain one.  Transition t of a block, shared state of `in` frozen:
+ *   amh_pooled_asss_ext_begin   for every chain at stream position in.i + t
+ *                         with the chain's key: the draws, y = S^-1 (x - mu)
+ *                         with the shared factor, projection, tangent, S z,
+ *                         S v; x(theta = 0) -> cand[0], x(theta_0) -> cand[1]
+ *                         (cand [2][C][d]); the chain's record -> work, in the
+ *                         layout of amh_asss_ext_begin (amh_asss_ext_work_size
+ *                         floats per chain; the shared mu copied per chain);
+ *                         zeroes active (AMH_ASSS_EXT_ROUNDS int32)
+ *   the caller's U of cand [2C, d], then amh_asss_ext_shrink(round 0), and
+ *   U of cand[1] and amh_asss_ext_shrink(round r + 1) while active[r] != 0,
+ *   exactly as for the per-chain sampler
+ *   amh_pooled_asss_ext_finish  per chain the outcome (x(0) with its U when
+ *                         capped or degenerate, else the accepted candidate
+ *                         with the U of the round that accepted it, NaN ->
+ *                         +inf) -> z_out / pe_out (may alias in's), and the
+ *                         transition's sums [S_d | S_dd | S_a | N = C] into
+ *                         sums (accumulate != 0: added to them), cut into the
+ *                         chunks of amh_pooled_asss_stats_k: with the same U
+ *                         the sums are that entry's at k_steps = 1 byte for
+ *                         byte.  `in` is the state begin read.
+ * A block of K transitions is K such sequences, t = 0 .. K - 1, the later ones
+ * reading the z / pe the previous finish wrote, accumulate = (t > 0): the
+ * block's sums are s_0 + s_1 + ... in step order (each transition's sums fully
+ * reduced first, as amh_pooled_stats_external below d = 64; not the fused
+ * kernel's in-chunk association).  After the exchange
+ *   amh_pooled_asss_ext_update  is amh_pooled_asss_update_k for an external
+ *                         handle.
+ * Nothing is kept in the handle between the calls.  AMH_EINVAL: a handle not
+ * bound to AMH_MODEL_EXTERNAL, dim > 64, null pointers, t < 0. */
+int amh_pooled_asss_ext_begin(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t t, float* cand,
+                              float* work, int32_t* active, void* stream);
+int amh_pooled_asss_ext_finish(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, const float* cand,
+                               const float* work, float* z_out, float* pe_out, double* sums, int32_t accumulate,
+                               void* stream);
+int amh_pooled_asss_ext_update(amh_handle* h, const double* sums, const amh_pooled_state* in,
+                               const amh_pooled_state* out, int32_t k_steps, void* stream);
+
 /* -------------------------------------------------------- exact sums ----
  * The sums above are added in double, in an order that depends on how many
  * chunks a rank holds, so two partitions of the same chains over ranks round

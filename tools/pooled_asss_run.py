@@ -7,7 +7,22 @@ PooledARWMH (d = 64 Gaussian: its MFMA form; d = 63 Gaussian and eight
 schools: the lane-per-row form PooledASSS shares) are timed in turn, `reps`
 times round robin, each window sized to about `window_s` seconds of steps and
 ended by a device synchronise.  Prints chain-steps/s and ms per block (median,
-min - max over the repetitions) and one JSON line."""
+min - max over the repetitions) and one JSON line.
+
+python3 tools/pooled_asss_run.py external [N]
+The cost of cutting the transition around a caller's potential: the d = 64
+Gaussian at C = 65,536, K = 1, one rank, PooledASSS(host_shrink=True) with the
+library's own Gaussian potential (amh_potential) behind the callable against
+the fused PooledASSS of the same build from the same start and key (the two
+runs are byte-identical).  After 20 transitions, three windows of N single
+transitions each (HIP events): seconds per transition (median, min - max), the
+mean and maximum shrink rounds per transition, and the ratio.
+
+python3 tools/pooled_asss_run.py legs [N]
+The two legs an A/B of two builds compares (select the build with
+AMH_LIB_PATH): the fused PooledASSS step at d = 64, C = 65,536, K = 1 and the
+per-chain ASSS(host_shrink=True) step at d = 64, C = 512 around the library's
+potential; one JSON line with us per transition of each."""
 import json
 import os
 import sys
@@ -19,8 +34,11 @@ import torch  # noqa: E402
 import posteriors as P  # noqa: E402
 from kernels_amd import ASSS, PooledARWMH, PooledASSS, PRNGKey  # noqa: E402
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-WINDOW = float(sys.argv[2]) if len(sys.argv) > 2 else 0.5
+MODE = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("external", "legs") else "shapes"
+ARGS = sys.argv[2:] if MODE != "shapes" else sys.argv[1:]
+REPS = int(ARGS[0]) if MODE == "shapes" and len(ARGS) > 0 else 5
+WINDOW = float(ARGS[1]) if MODE == "shapes" and len(ARGS) > 1 else 0.5
+N = int(ARGS[0]) if MODE != "shapes" and len(ARGS) > 0 else 100
 
 
 def make(cls, shape, C, K):
@@ -68,5 +86,72 @@ def main():
     print(json.dumps(dict(device=torch.cuda.get_device_name(0), reps=REPS, rows=out)))
 
 
+def timed(step, n):
+    """us per call of `step` over one window of n calls (HIP events)."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(n):
+        step()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3
+
+
+def library_potential(d):
+    """The library's Gaussian potential as a plain callable."""
+    kg = ASSS(potential_fn=P.correlated_gaussian(d), num_chains=8)
+    kg.init(PRNGKey(1), 0, torch.zeros(8, d), (), {})
+    return lambda z: kg.potential(z)
+
+
+def external():
+    d, C = 64, 65536
+    z0 = (torch.rand(C, d, device="cuda") * 4 - 2).contiguous()
+    kf = PooledASSS(potential_fn=P.correlated_gaussian(d), num_chains=C)
+    sf = kf.init(PRNGKey(0), 0, z0, (), {})
+    ke = PooledASSS(potential_fn=library_potential(d), num_chains=C, host_shrink=True)
+    se = ke.init(PRNGKey(0), 0, z0, (), {})
+    kf.sample_(sf, 20)
+    ke.sample_(se, 20)
+    rounds = []
+
+    def ext_step():
+        ke.sample_(se, 1)
+        rounds.append(ke.shrink_rounds)
+
+    te, tf = [], []
+    for _ in range(3):
+        te.append(timed(ext_step, N))
+        tf.append(timed(lambda: kf.sample_(sf, 1), N))
+    torch.cuda.synchronize()
+    same = bool(torch.equal(se.z, sf.z)) and bool(torch.equal(se.adapt_state.scale, sf.adapt_state.scale))
+    te.sort()
+    tf.sort()
+    r = torch.tensor(rounds, dtype=torch.float64)
+    rec = dict(mode="external", d=d, C=C, K=1, n=N, external_s=te[1] * 1e-6, external_lo_s=te[0] * 1e-6,
+               external_hi_s=te[2] * 1e-6, fused_s=tf[1] * 1e-6, fused_lo_s=tf[0] * 1e-6, fused_hi_s=tf[2] * 1e-6,
+               ratio=te[1] / tf[1], rounds_mean=float(r.mean()), rounds_max=int(r.max()), same_bytes=same)
+    print(f"d={d} C={C} K=1: external {rec['external_s']:.3e} s per transition ({te[0] * 1e-6:.3e} - "
+          f"{te[2] * 1e-6:.3e}), rounds mean {rec['rounds_mean']:.2f} max {rec['rounds_max']}; fused "
+          f"{rec['fused_s']:.3e} s ({tf[0] * 1e-6:.3e} - {tf[2] * 1e-6:.3e}); ratio {rec['ratio']:.1f}; "
+          f"states byte-equal: {same}")
+    print(json.dumps(dict(device=torch.cuda.get_device_name(0), **rec)))
+
+
+def legs():
+    d = 64
+    kf = PooledASSS(potential_fn=P.correlated_gaussian(d), num_chains=65536)
+    sf = kf.init(PRNGKey(0), 0, (torch.rand(65536, d, device="cuda") * 4 - 2).contiguous(), (), {})
+    kf.sample_(sf, 20)
+    ka = ASSS(potential_fn=library_potential(d), num_chains=512, host_shrink=True)
+    sa = ka.init(PRNGKey(0), 0, (torch.rand(512, d, device="cuda") * 4 - 2).contiguous(), (), {})
+    ka.sample_(sa, 100)
+    tf = sorted(timed(lambda: kf.sample_(sf, 1), 4 * N) for _ in range(3))
+    ta = sorted(timed(lambda: ka.sample_(sa, 1), N) for _ in range(3))
+    print(json.dumps(dict(mode="legs", lib=os.environ.get("AMH_LIB_PATH", "release"), n=N,
+                          pooled_asss_fused_us=tf[1], asss_host_shrink_us=ta[1])))
+
+
 if __name__ == "__main__":
-    main()
+    dict(shapes=main, external=external, legs=legs)[MODE]()
