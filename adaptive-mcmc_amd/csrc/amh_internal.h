@@ -30,7 +30,7 @@ inline int cu_count() {
 struct ModelArgs {
   const float* data;  // device, model-specific layout (include/amh.h)
   int64_t n;          // N rows (regression models)
-  int64_t k;          // K columns (diamonds)
+  int64_t k;          // K columns (diamonds, logistic)
 };
 
 struct StepParams {
@@ -75,7 +75,7 @@ struct PotParams {
   int64_t n;
   int32_t d;
   ModelArgs model;
-  const float* xpack = nullptr;  // diamonds: the design matrix in MFMA tile order (diamonds_pack_kernel)
+  const float* xpack = nullptr;  // diamonds, logistic: the design matrix in MFMA tile order (*_pack_kernel)
 };
 
 struct PnxParams {
@@ -358,6 +358,9 @@ bool split_model(int model_id, int d);
 constexpr int kDiaMfmaKc = 24;  // diamonds on MFMA: the reference data set's Kc (amh_split.hip)
 int64_t diamonds_pack_floats(int64_t N, int64_t K);  // 0: no MFMA path for this shape
 hipError_t run_diamonds_pack(const ModelArgs& m, float* xp, hipStream_t s);
+// logistic regression on MFMA: the tile copy of X and y for any 1 <= K <= 31 (amh_split.hip)
+int64_t logistic_pack_floats(int64_t N, int64_t K);
+hipError_t run_logistic_pack(const ModelArgs& m, float* xp, hipStream_t s);
 // the reference diamonds data (K = 25 columns): d = 26, compiled as a fixed
 // dimension on the split path
 constexpr int kDiamondsD = 26;

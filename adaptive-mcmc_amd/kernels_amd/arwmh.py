@@ -353,11 +353,14 @@ class ARWMH:
 
     def _chained_path(self) -> bool:
         """Paths whose step pass forms the next transition's proposal: d > 64
-        (amh_big.hip) and the literal diamonds model's split transition
-        (amh_split.hip; include/amh.h AMH_STEP_KEEP_PROPOSAL)."""
+        (amh_big.hip) and the split transition of the literal diamonds model
+        and of logistic regression (amh_split.hip; include/amh.h
+        AMH_STEP_KEEP_PROPOSAL)."""
         if self._dim > 64:
             return True
         mid = self._model.model_id if self._model is not None else self._potential_fn.model_id
+        if mid == _lib.AMH_MODEL_LOGISTIC:  # always split (2 <= d <= 32)
+            return True
         return mid == _lib.AMH_MODEL_DIAMONDS and 3 <= self._dim <= 32
 
     def potential(self, z: torch.Tensor) -> torch.Tensor:

@@ -313,12 +313,45 @@ class PooledARWMH(ARWMH):
                 cur = AmhPooledState.from_buffer_copy(cin)
                 cur.z, cur.potential_energy = sout.z.data_ptr(), sout.potential_energy.data_ptr()
 
+    def _step_order_block(self) -> bool:
+        """Logistic regression at sync_every > 1: the block runs as K
+        single-step stats launches whose completely reduced sums are added in
+        step order -- the callable path's association (include/amh.h,
+        amh_pooled_stats_external), so PooledARWMH(model=entry) equals
+        PooledARWMH(potential_fn=its potential) bit for bit at every
+        sync_every.  The other registry models keep the one-launch block, whose
+        sums are associated inside the chunk."""
+        return self.sync_every > 1 and self._model is not None and \
+            self._model.model_id == _lib.AMH_MODEL_LOGISTIC
+
+    def _stats_step_order(self, L, cin, sout, b, C):
+        dev = sout.z.device
+        h, st = self._handle.h, _lib.stream_ptr(dev.index)
+        cur = AmhPooledState.from_buffer_copy(cin)
+        total = self._acc[b] if self.exact_sums else self._bufs[b]
+        part = torch.empty_like(total)
+        for t in range(self.sync_every):
+            it = self._block_i + t  # the step's noise position; the shared state stays frozen
+            cur.i = it.data_ptr()
+            into = total if t == 0 else part
+            out = (_lib.ptr(sout.z), _lib.ptr(sout.potential_energy), _lib.ptr(into), st)
+            if self.exact_sums:
+                rc = L.amh_pooled_stats_k_exact(h, C, self._total, ctypes.byref(cur), 1, *out)
+            else:
+                rc = L.amh_pooled_stats_k(h, C, ctypes.byref(cur), 1, *out)
+            _lib.check(rc, h)
+            if t > 0:
+                total += part
+            cur.z, cur.potential_energy = sout.z.data_ptr(), sout.potential_energy.data_ptr()
+
     def _stats(self, L, cin, sout, b, C):
         """The block's transitions and this rank's sums into buffer b (its
         float64 sums, or with exact_sums its int64 words)."""
         dev = sout.z.device.index
         if self._external():
             return self._stats_external(L, cin, sout, b, C)
+        if self._step_order_block():
+            return self._stats_step_order(L, cin, sout, b, C)
         if self.exact_sums:
             _lib.check(L.amh_pooled_stats_k_exact(self._handle.h, C, self._total, ctypes.byref(cin), self.sync_every,
                                                   _lib.ptr(sout.z), _lib.ptr(sout.potential_energy),
@@ -338,6 +371,7 @@ class PooledARWMH(ARWMH):
         dev = sin.z.device.index
         C = sin.z.shape[0]
         cin, cout = self._c(sin), self._c(sout)
+        self._block_i = sin.i  # the block's first noise position (_stats_step_order)
         with torch.cuda.device(dev):
             if not self.overlap:
                 buf = self._bufs[0]
@@ -431,7 +465,7 @@ class PooledARWMH(ARWMH):
         if int(n_steps) % K != 0:
             raise ValueError(f"n_steps ({n_steps}) must be a multiple of sync_every ({K})")
         if (self._world() == 1 and not self.overlap and not self.force_collective and not self._external()
-                and not self.exact_sums):
+                and not self.exact_sums and not self._step_order_block()):
             L = _lib.lib()
             dev = state.z.device.index
             c = self._c(state)

@@ -58,7 +58,8 @@ class PooledASSS(PooledARWMH):
     Limits (ValueError): d <= 64; a callable potential_fn needs
     host_shrink=True (the fused slice transition evaluates the potential
     inside the kernel), and host_shrink=True needs a callable; no
-    exact_sums."""
+    exact_sums; not the logistic_regression model (the pooled slice kernel has
+    no instantiation for it)."""
 
     def __init__(self, model=None, potential_fn=None, lr_decay=2 / 3, eps=1e-6, num_chains=None, device=None,
                  chain_offset=0, group=None, sync_every: int = 1, overlap: bool = False, exact_sums: bool = False,
@@ -71,6 +72,10 @@ class PooledASSS(PooledARWMH):
         if self._host_shrink and not callable_fn:
             raise ValueError("host_shrink=True is for a callable potential_fn; a model or a registry potential "
                              "runs inside the slice kernel")
+        if model is not None and getattr(model, "model_id", None) == _lib.AMH_MODEL_LOGISTIC:
+            raise ValueError("PooledASSS has no slice kernel for the logistic_regression model (the pooled slice "
+                             "kernels are instantiated per model); use ASSS, PooledARWMH, or its potential as a "
+                             "callable with host_shrink=True")
         if exact_sums:
             raise ValueError("PooledASSS has no exact fixed-point sums (exact_sums=True)")
         super().__init__(model=model, potential_fn=potential_fn, lr_decay=lr_decay, eps=eps, num_chains=num_chains,

@@ -10,8 +10,9 @@ Python callable, so each model here is a registry entry that knows
   * how to map unconstrained draws back to constrained sites (postprocess).
 
 Entries: eight_schools (non-centred), kidiq_kidscore_momhsiq, diamonds, a
-dense Gaussian potential (the build's benchmark targets) and the notebook's
-normal mixture potential (asumptions_check.ipynb cells 61-62).
+dense Gaussian potential (the build's benchmark targets), the notebook's
+normal mixture potential (asumptions_check.ipynb cells 61-62) and logistic
+regression on the caller's own data (logistic_regression(X, y)).
 """
 from __future__ import annotations
 
@@ -192,6 +193,107 @@ def synthetic_diamonds(N: int = 5000, K: int = 25, seed: int = 26) -> dict:
     Xc = X[:, 1:] - X[:, 1:].mean(axis=0)
     Y = (7.79 + Xc @ b + 0.123 * rng.normal(size=N)).astype(np.float32)
     return {"Y": Y, "X": X}
+
+
+# ------------------------------------------------------- logistic regression --
+# The caller's own data set (no counterpart in the reference, whose models are
+# the three PosteriorDB scripts): include/amh.h AMH_MODEL_LOGISTIC.
+class LogisticRegression(Model):
+    """Bayesian logistic regression on the caller's data: y_n ~ Bernoulli(
+    logit^-1(Intercept + X_n b)), Intercept ~ N(0, intercept_scale), b_k ~
+    N(0, prior_scale).  It has the object shape of `diamonds` (a `Model`, used
+    as ARWMH(model=...), sites Intercept and b) but carries its data itself, so
+    `model_kwargs` stays empty and every method's `data` argument is ignored."""
+
+    def __init__(self, X: np.ndarray, y: np.ndarray, prior_scale: float, intercept_scale: float):
+        self.X, self.y = X, y  # float32, as the device reads them
+        self.N, self.K = X.shape
+        self.prior_scale, self.intercept_scale = float(prior_scale), float(intercept_scale)
+        sI, sb = self.intercept_scale, self.prior_scale
+        # iI2, ib2, c0: float64 on the host, then rounded (as the mixture's c_k)
+        self.consts = np.array([1.0 / (sI * sI), 1.0 / (sb * sb),
+                                math.log(sI * math.sqrt(2.0 * math.pi)) +
+                                self.K * math.log(sb * math.sqrt(2.0 * math.pi))], np.float64).astype(np.float32)
+        super().__init__("logistic_regression", _lib.AMH_MODEL_LOGISTIC, self._sites, self._pack, None,
+                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Bernoulli(logit^-1(Intercept + X b))")
+
+    def _sites(self, data=None):
+        return [Site("Intercept", 1), Site("b", self.K)]
+
+    def _pack(self, data=None):
+        return np.concatenate([self.X.reshape(-1), self.y, self.consts]), (self.N, self.K)
+
+    def sites(self, data: dict = None) -> List[Site]:
+        return self._sites()
+
+    def dim(self, data: dict = None) -> int:
+        return self.K + 1
+
+    def pack(self, data: dict = None, device="cpu") -> Tuple[torch.Tensor, Tuple[int, ...]]:
+        return super().pack(data, device)
+
+    def unravel(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
+        # b keeps its axis at K = 1 (a Site of size 1 would lose it)
+        return {"Intercept": z[..., 0], "b": z[..., 1:self.K + 1]}
+
+    def postprocess(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
+        return self.unravel(z)
+
+
+def logistic_regression(X, y, prior_scale: float = 2.5, intercept_scale: float = 10.0) -> LogisticRegression:
+    """Registry entry for ARWMH / ASSS / PooledARWMH(model=...) and MCMC, with
+    X [N, K] (1 <= K <= 31, no intercept column: the model has its own) and y
+    [N] in {0, 1}; the data travel with the entry (init's model_kwargs = {})."""
+    Xa = np.asarray(_np(X))
+    if Xa.ndim != 2:
+        raise ValueError(f"X must be 2-D [N, K], not {Xa.ndim}-D")
+    N, K = Xa.shape
+    if N < 1:
+        raise ValueError("X needs at least one row")
+    if not 1 <= K <= 31:
+        raise ValueError(f"logistic_regression supports 1 <= K <= 31 predictors, not K = {K}")
+    with np.errstate(over="ignore"):  # a value past float32 becomes inf and is refused below
+        Xa = np.ascontiguousarray(Xa, dtype=np.float32)
+    if not np.all(np.isfinite(Xa)):
+        raise ValueError("X must be finite (in float32)")
+    ya = np.asarray(_np(y)).reshape(-1)
+    if ya.shape[0] != N:
+        raise ValueError(f"y has {ya.shape[0]} entries for {N} rows of X")
+    if not np.all((ya == 0) | (ya == 1)):
+        raise ValueError("every y must be 0 or 1")
+    if not (float(prior_scale) > 0 and math.isfinite(float(prior_scale))):
+        raise ValueError("prior_scale must be positive")
+    if not (float(intercept_scale) > 0 and math.isfinite(float(intercept_scale))):
+        raise ValueError("intercept_scale must be positive")
+    return LogisticRegression(Xa, ya.astype(np.float32), prior_scale, intercept_scale)
+
+
+def logistic_potential_f64(z, entry: LogisticRegression) -> torch.Tensor:
+    """U of `entry` in float64 on the float32 data and constants the device
+    reads: sum_n [softplus(eta_n) - y_n eta_n] + b'b ib2 / 2 + I^2 iI2 / 2 + c0
+    for z [..., K + 1] (a torch tensor on any device, or an array)."""
+    z = torch.as_tensor(z).to(torch.float64)
+    dev = z.device
+    X = torch.as_tensor(entry.X, device=dev).to(torch.float64)
+    y = torch.as_tensor(entry.y, device=dev).to(torch.float64)
+    iI2, ib2, c0 = (float(v) for v in entry.consts)
+    icpt, b = z[..., 0], z[..., 1:]
+    eta = icpt[..., None] + b @ X.T
+    t = torch.logaddexp(eta, torch.zeros_like(eta)) - y * eta
+    return t.sum(-1) + 0.5 * (b * b).sum(-1) * ib2 + 0.5 * icpt * icpt * iI2 + c0
+
+
+def synthetic_logistic(N: int = 5000, K: int = 24, seed: int = 8) -> dict:
+    """Synthetic logistic-regression data: standard normal predictors with
+    pairwise correlation 0.3, y ~ Bernoulli(logit^-1(0.5 + X b*)), b* ~
+    N(0, 0.5).  Returns {"X": [N, K] float32, "y": [N] float32 in {0, 1}}."""
+    rng = np.random.default_rng(seed)
+    f = rng.normal(size=(N, 1))
+    X = (math.sqrt(0.3) * f + math.sqrt(0.7) * rng.normal(size=(N, K))).astype(np.float32)
+    b = rng.normal(0.0, 0.5, size=K)
+    p = 1.0 / (1.0 + np.exp(-(0.5 + X.astype(np.float64) @ b)))
+    y = (rng.random(N) < p).astype(np.float32)
+    return {"X": X, "y": y}
 
 
 # ------------------------------------------------------------------ gaussian --
