@@ -49,7 +49,7 @@ struct amh_handle {
   amh::ModelArgs model{nullptr, 0, 0};
   int64_t n_data = 0;
   float* gamma_tab = nullptr;  // device, kGammaTab entries
-  float* xpack = nullptr;      // diamonds, logistic: design matrix in MFMA tile order (made by amh_bind_model)
+  float* xpack = nullptr;      // diamonds, logistic, poisson: design matrix in MFMA tile order (made by amh_bind_model)
   amh::Scratch partials;       // pooled mode: chunk partial sums
   amh::Scratch split;          // split path: proposals [C][d] then U(z') [C]; d > 64: xprop, wa, wr, dg [C][d]
                                // then U(z') [C]; pooled d > 64: the A-operand copies (pooled_big_pack_floats)
@@ -181,6 +181,14 @@ int expected_dim(int model_id, int64_t n_data, const int64_t* ip, int nip, int d
       if (K < 1 || K > 31) { *why = "logistic needs 1 <= K <= 31 predictors"; return -1; }
       if (N < 1) { *why = "logistic needs N >= 1 rows"; return -1; }
       if (n_data != N * K + N + 3) { *why = "logistic data must hold N*K + N + 3 floats"; return -1; }
+      return (int)(K + 1);
+    }
+    case AMH_MODEL_POISSON: {
+      if (nip < 2) { *why = "poisson needs iparams {N, K}"; return -1; }
+      const int64_t N = ip[0], K = ip[1];
+      if (K < 1 || K > 31) { *why = "poisson needs 1 <= K <= 31 predictors"; return -1; }
+      if (N < 1) { *why = "poisson needs N >= 1 rows"; return -1; }
+      if (n_data != N * K + 2 * N + 3) { *why = "poisson data must hold N*K + 2*N + 3 floats"; return -1; }
       return (int)(K + 1);
     }
     case AMH_MODEL_MIXTURE: {
@@ -502,21 +510,25 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
   h->model_id = 0;  // unbound until the whole binding has succeeded
   h->model.data = data;
   const bool dia = model_id == AMH_MODEL_DIAMONDS || model_id == AMH_MODEL_DIAMONDS_SS ||
-                   model_id == AMH_MODEL_LOGISTIC;  // iparams {N, K}
+                   model_id == AMH_MODEL_LOGISTIC || model_id == AMH_MODEL_POISSON;  // iparams {N, K}
   h->model.n = (model_id == AMH_MODEL_KIDIQ || model_id == AMH_MODEL_MIXTURE || dia) ? iparams[0] : 0;
   h->model.k = dia ? iparams[1] : 0;
   h->n_data = n_data;
-  if ((model_id == AMH_MODEL_DIAMONDS || model_id == AMH_MODEL_LOGISTIC) && amh::split_model(model_id, dm)) {
+  if ((model_id == AMH_MODEL_DIAMONDS || model_id == AMH_MODEL_LOGISTIC || model_id == AMH_MODEL_POISSON) &&
+      amh::split_model(model_id, dm)) {
     // the MFMA potential's tile copy of the design matrix and the response, made
     // once here (synchronous, on the null stream: the caller has synchronised the
     // stream that wrote data)
-    const bool lg = model_id == AMH_MODEL_LOGISTIC;
-    const int64_t nf = lg ? amh::logistic_pack_floats(h->model.n, h->model.k)
-                          : amh::diamonds_pack_floats(h->model.n, h->model.k);
+    const bool lg = model_id == AMH_MODEL_LOGISTIC, po = model_id == AMH_MODEL_POISSON;
+    const int64_t nf = lg   ? amh::logistic_pack_floats(h->model.n, h->model.k)
+                       : po ? amh::poisson_pack_floats(h->model.n, h->model.k)
+                            : amh::diamonds_pack_floats(h->model.n, h->model.k);
     if (nf > 0) {
       hipError_t e = hipMalloc(&h->xpack, (size_t)nf * sizeof(float));
       if (e == hipSuccess)
-        e = lg ? amh::run_logistic_pack(h->model, h->xpack, nullptr) : amh::run_diamonds_pack(h->model, h->xpack, nullptr);
+        e = lg   ? amh::run_logistic_pack(h->model, h->xpack, nullptr)
+            : po ? amh::run_poisson_pack(h->model, h->xpack, nullptr)
+                 : amh::run_diamonds_pack(h->model, h->xpack, nullptr);
       if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
       if (e != hipSuccess) {
         if (h->xpack) (void)hipFree(h->xpack);

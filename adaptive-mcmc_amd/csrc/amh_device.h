@@ -600,6 +600,54 @@ struct LogisticM {
   }
 };
 
+// One row's term of the Poisson log-link potential (AMH_MODEL_POISSON):
+// exp(eta) - y eta, the product rounded before the difference.  The group
+// kernel and the MFMA kernel (amh_split.hip) both call this.
+__device__ __forceinline__ float poisson_term(float eta, float y) { return amh_expf(eta) - (y * eta); }
+
+template <int G>
+struct PoissonM {
+  // z = [Intercept, b (K)]; data = [X (N x K) | y (N) | o (N) | iI2, ib2, c0]
+  // Straight VALU restatement with the shape of LogisticM: 32 partial sums
+  // whatever the group width, lane r < 32 sums rows n = r, r + 32, ..., and the
+  // lanes above 32 of a G = 64 group (the pooled kernels) hold +0.
+  static_assert(G >= 32, "the Poisson model runs at lane-group width 32 (64 in the pooled kernels)");
+  struct Ctx {
+    int64_t N;
+    const float* data;
+  };
+  static __host__ __device__ size_t lds_bytes(const ModelArgs&, int) { return 0; }
+  static __device__ void stage(float*, const ModelArgs&, int) {}
+  static __device__ __forceinline__ Ctx prepare(const ModelArgs& m, int, int) { return Ctx{m.n, m.data}; }
+  static __device__ __forceinline__ float potential(float x, int r, int d, const Ctx& c, const float*) {
+    const int64_t N = c.N;
+    const int K = d - 1;
+    const float* X = c.data;
+    const float* Y = X + N * K;
+    const float* O = Y + N;
+    const float* pr = O + N;  // iI2, ib2, c0
+    float xb[32];
+    static_for<32>([&](auto J) { xb[J] = Grp<G>::template bcast<J>(x); });
+    const float icpt = xb[0];
+    float acc = 0.0f;
+    if (r < 32) {
+      for (int64_t n = r; n < N; n += 32) {
+        float m = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 31; ++k) {
+          if (k >= K) continue;
+          m = fmaf(X[n * K + k], xb[1 + k], m);
+        }
+        acc = acc + poisson_term((icpt + m) + O[n], Y[n]);
+      }
+    }
+    const float S = Grp<G>::sum(acc);
+    const float bb = (r >= 1 && r <= K) ? x * x : 0.0f;
+    const float B = Grp<G>::sum(bb);
+    return ((S + (0.5f * B) * pr[1]) + (0.5f * (icpt * icpt)) * pr[0]) + pr[2];
+  }
+};
+
 // Diamonds through sufficient statistics (AMH_MODEL_DIAMONDS_SS).  The
 // likelihood's residual sum is an exact quadratic in (Intercept, b):
 //   sum_n (Y_n - I - Xc_n b)^2 = A + a (N a - 2 sT) - 2 b'(t - a sx) + b'Gm b,
@@ -896,7 +944,7 @@ __device__ __forceinline__ float capture(float old, float v, int rr) {
 // Dispatch table over (model, d).  Instantiated shapes:
 //   Gaussian: exact d = 64 (headline), dynamic d <= 1,2,4,8,16,32,64
 //   eight schools: d <= 16;  kidiq: d = 4;  diamonds: d <= 32;
-//   logistic: 2 <= d <= 32, always at G = 32
+//   logistic, poisson: 2 <= d <= 32, always at G = 32
 template <template <int> class M, class F>
 static hipError_t dispatch_dim(int d, bool allow_exact64, F&& f) {
   if (d < 1 || d > 64) return hipErrorInvalidValue;
@@ -937,6 +985,9 @@ static hipError_t dispatch(int model_id, int d, F&& f) {
     case AMH_MODEL_LOGISTIC:
       if (d < 2 || d > 32) return hipErrorInvalidValue;
       return f.template operator()<32, LogisticM, false>();
+    case AMH_MODEL_POISSON:
+      if (d < 2 || d > 32) return hipErrorInvalidValue;
+      return f.template operator()<32, PoissonM, false>();
     default:
       return hipErrorInvalidValue;
   }

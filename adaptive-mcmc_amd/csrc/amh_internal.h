@@ -30,7 +30,7 @@ inline int cu_count() {
 struct ModelArgs {
   const float* data;  // device, model-specific layout (include/amh.h)
   int64_t n;          // N rows (regression models)
-  int64_t k;          // K columns (diamonds, logistic)
+  int64_t k;          // K columns (diamonds, logistic, poisson)
 };
 
 struct StepParams {
@@ -75,7 +75,7 @@ struct PotParams {
   int64_t n;
   int32_t d;
   ModelArgs model;
-  const float* xpack = nullptr;  // diamonds, logistic: the design matrix in MFMA tile order (*_pack_kernel)
+  const float* xpack = nullptr;  // diamonds, logistic, poisson: the design matrix in MFMA tile order (*_pack_kernel)
 };
 
 struct PnxParams {
@@ -361,6 +361,9 @@ hipError_t run_diamonds_pack(const ModelArgs& m, float* xp, hipStream_t s);
 // logistic regression on MFMA: the tile copy of X and y for any 1 <= K <= 31 (amh_split.hip)
 int64_t logistic_pack_floats(int64_t N, int64_t K);
 hipError_t run_logistic_pack(const ModelArgs& m, float* xp, hipStream_t s);
+// Poisson regression on MFMA: the tile copy of X, y and the offset, same limits (amh_split.hip)
+int64_t poisson_pack_floats(int64_t N, int64_t K);
+hipError_t run_poisson_pack(const ModelArgs& m, float* xp, hipStream_t s);
 // the reference diamonds data (K = 25 columns): d = 26, compiled as a fixed
 // dimension on the split path
 constexpr int kDiamondsD = 26;

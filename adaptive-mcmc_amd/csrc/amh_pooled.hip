@@ -369,6 +369,9 @@ hipError_t run_pooled_stats(int model_id, const PooledStatsParams& p, double* su
     case AMH_MODEL_LOGISTIC:
       if (d < 2 || d > 32) return hipErrorInvalidValue;
       return f.template operator()<64, LogisticM, false>();
+    case AMH_MODEL_POISSON:
+      if (d < 2 || d > 32) return hipErrorInvalidValue;
+      return f.template operator()<64, PoissonM, false>();
     default:
       return hipErrorInvalidValue;
   }

@@ -205,6 +205,8 @@ bool pooled_asss_model(int model_id, int d) {
       return d >= 1 && d <= 64;
     case AMH_MODEL_DIAMONDS_SS:
       return d >= 3 && d <= 32;
+    case AMH_MODEL_POISSON:
+      return d >= 2 && d <= 32;
     default:
       return false;
   }
@@ -222,6 +224,8 @@ hipError_t run_pooled_asss_stats(int model_id, const PooledStatsParams& p, doubl
       return launch_pooled_asss_stats<KidiqM>(p, sums, s);
     case AMH_MODEL_DIAMONDS:
       return launch_pooled_asss_stats<DiamondsM>(p, sums, s);
+    case AMH_MODEL_POISSON:
+      return launch_pooled_asss_stats<PoissonM>(p, sums, s);
     default:
       return launch_pooled_asss_stats<DiamondsSSM>(p, sums, s);
   }

@@ -1,5 +1,5 @@
 // amh_split.hip -- the split transition for data-heavy models (diamonds,
-// logistic regression).
+// logistic and Poisson regression).
 //
 // The fused step kernel evaluates the potential with the chain's lane group
 // (lane r sums rows n = r, r+G, ...), so every chain streams the whole data
@@ -26,7 +26,7 @@
 namespace amh {
 
 bool split_model(int model_id, int d) {
-  if (model_id == AMH_MODEL_LOGISTIC) return d >= 2 && d <= 32;
+  if (model_id == AMH_MODEL_LOGISTIC || model_id == AMH_MODEL_POISSON) return d >= 2 && d <= 32;
   return model_id == AMH_MODEL_DIAMONDS && d >= 3 && d <= 32;
 }
 
@@ -578,6 +578,189 @@ static hipError_t run_logistic_potential(const PotParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------- Poisson on MFMA --
+// AMH_MODEL_POISSON: a sibling of the logistic kernel above with the same
+// geometry (A = a 32-row tile of X, B = the coefficients of 32 chains, GV =
+// ceil(K / 8) A vectors per lane and tile, columns k >= K zero in both
+// operands, register R of lane (i, h) = row 32 m + (R&3) + 8 (R>>2) + 4 h of
+// chain i).  The epilogue on the accumulator registers is eta = (I + m) + o,
+// t = poisson_term(eta, y), part[R] = part[R] + t.  Rows at or past N are left
+// out by a select on the register's row: their term is e^I, not 0.  The tile
+// copy: per tile GV * 256 floats of X in A-operand order, then per tile 64
+// floats, y and then the offset, each 32 in register order
+// (poisson_pack_kernel, made when the model is bound).
+struct PoiMfma {
+  static constexpr int gv(int64_t K) { return LogMfma::gv(K); }
+  static constexpr int64_t tiles(int64_t N) { return LogMfma::tiles(N); }
+  static constexpr int64_t floats(int64_t N, int64_t K) { return tiles(N) * (gv(K) * 256 + 64); }
+};
+
+__global__ __launch_bounds__(256) void poisson_pack_kernel(const float* __restrict__ data, int64_t N, int K,
+                                                           float* __restrict__ xp) {
+  const int GV = PoiMfma::gv(K);
+  const int64_t NT = PoiMfma::tiles(N);
+  const int64_t m = blockIdx.x;
+  const int t = threadIdx.x;
+  const float* X = data;
+  const float* YO = data + N * K;  // y (N), then o (N)
+  if (t < GV * 64) {
+    const int g = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
+    const int64_t row = 32 * m + i;
+    f32x4 v;
+    static_for<4>([&](auto E) {
+      const int k = 2 * (4 * g + E) + h;
+      v[(int)E] = (row < N && k < K) ? X[row * K + k] : 0.0f;
+    });
+    ((f32x4*)xp)[(m * GV + g) * 64 + lane] = v;
+  }
+  if (t >= 256 - 64) {
+    const int q = t - (256 - 64), which = q >> 5, h = (q >> 4) & 1, R = q & 15;
+    const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;
+    xp[NT * GV * 256 + 64 * m + q] = row < N ? YO[which * N + row] : 0.0f;
+  }
+}
+
+template <int GV>
+__global__ __launch_bounds__(256, 2) void poisson_pot_mfma_kernel(PotParams p) {
+  constexpr int S = 4 * GV, NB = kLogNB;
+  const int d = p.d;
+  const int K = d - 1;
+  const int64_t N = p.model.n;
+  const int64_t NT = PoiMfma::tiles(N);
+  const int64_t n_ch = p.n;
+  const int lane = lane_id();
+  const int i = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+  const int64_t cb = ((int64_t)blockIdx.x * 4 + w) * (32 * NB);
+  int64_t cq[NB];
+  const float* zq[NB];
+  float B[NB][S];
+  float icq[NB];
+  static_for<NB>([&](auto J) {
+    cq[J] = cb + 32 * J + i;
+    zq[J] = p.z + (cq[J] < n_ch ? cq[J] : n_ch - 1) * d;
+    static_for<S>([&](auto Q) {
+      const int k = 2 * Q + h;
+      B[J][Q] = k < K ? zq[J][1 + k] : 0.0f;
+    });
+    icq[J] = zq[J][0];
+  });
+  const f32x4* xa = (const f32x4*)p.xpack + lane;
+  const f32x4* ya = (const f32x4*)(p.xpack + NT * GV * 256) + 4 * h;  // y; the offset 8 vectors on
+  float part[NB][16];
+  static_for<NB>([&](auto J) { static_for<16>([&](auto R) { part[J][R] = 0.0f; }); });
+  f32x4 a[GV], y[4], o[4];
+  static_for<GV>([&](auto Q) { a[Q] = xa[64 * Q]; });
+  static_for<4>([&](auto Q) {
+    y[Q] = ya[Q];
+    o[Q] = ya[8 + Q];
+  });
+  // one tile: the MFMA steps of each B tile, then the epilogue; FULL: every
+  // row exists (all tiles but the last: no per-register row test)
+  auto tile = [&](int64_t m, auto FULL) {
+    f32x4 an[GV], yn[4], on[4];
+    const int64_t mn = (m + 1 < NT) ? m + 1 : m;  // next tile's loads in flight during this one
+    static_for<GV>([&](auto Q) { an[Q] = xa[(mn * GV + Q) * 64]; });
+    static_for<4>([&](auto Q) {
+      yn[Q] = ya[16 * mn + Q];
+      on[Q] = ya[16 * mn + 8 + Q];
+    });
+    f32x16 acc[NB];
+    static_for<NB>([&](auto J) { acc[J] = f32x16{}; });
+    static_for<S>([&](auto Q) {
+      const float av = a[Q / 4][Q % 4];
+      static_for<NB>([&](auto J) { acc[J] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B[J][Q], acc[J], 0, 0, 0); });
+    });
+    const int64_t nrem = N - 32 * m;  // rows of this tile that exist
+    static_for<16>([&](auto R) {
+      const int rr = (R & 3) + 8 * (R >> 2) + 4 * h;
+      const float yv = y[R / 4][R % 4], ov = o[R / 4][R % 4];
+      static_for<NB>([&](auto J) {
+        const float t = poisson_term((icq[J] + acc[J][(int)R]) + ov, yv);
+        if constexpr (decltype(FULL)::value) {
+          part[J][R] = part[J][R] + t;
+        } else {
+          part[J][R] = (rr < nrem) ? part[J][R] + t : part[J][R];
+        }
+      });
+    });
+    static_for<GV>([&](auto Q) { a[Q] = an[Q]; });
+    static_for<4>([&](auto Q) {
+      y[Q] = yn[Q];
+      o[Q] = on[Q];
+    });
+  };
+#pragma unroll 1
+  for (int64_t m = 0; m + 1 < NT; ++m) tile(m, std::true_type{});
+  if (NT > 0) tile(NT - 1, std::false_type{});
+  // chain pair (2P, 2P + 1): lane (i, 0) finishes chain 2P, lane (i, 1) chain
+  // 2P + 1; the other half's residues arrive by a 32-lane swap
+  const float* pr = p.model.data + N * K + 2 * N;  // iI2, ib2, c0
+  const float iI2 = pr[0], ib2 = pr[1], c0 = pr[2];
+  static_for<NB / 2>([&](auto PP) {
+    constexpr int P0 = 2 * PP, P1 = 2 * PP + 1;
+    float all[32];
+    static_for<16>([&](auto R) {
+      const float mine = h ? part[P1][R] : part[P0][R];
+      const float other = __shfl_xor(h ? part[P0][R] : part[P1][R], 32, 64);
+      const int rm = (R & 3) + 8 * (R >> 2);
+      if (h == 0) {
+        all[rm] = mine;
+        all[rm + 4] = other;
+      } else {
+        all[rm + 4] = mine;
+        all[rm] = other;
+      }
+    });
+    const float Ssum = butterfly32(all);
+    const int64_t c = h ? cq[P1] : cq[P0];
+    const float* zc = h ? zq[P1] : zq[P0];
+    float bb[32];
+    static_for<32>([&](auto R) {
+      constexpr int r = R;
+      if constexpr (r >= 1) {
+        const float br = zc[r <= K ? r : 0];
+        bb[r] = (r <= K) ? br * br : 0.0f;
+      } else {
+        bb[r] = 0.0f;
+      }
+    });
+    const float Bsum = butterfly32(bb);
+    const float icpt = zc[0];
+    if (c < n_ch) p.pe[c] = ((Ssum + (0.5f * Bsum) * ib2) + (0.5f * (icpt * icpt)) * iI2) + c0;
+  });
+}
+
+int64_t poisson_pack_floats(int64_t N, int64_t K) { return (N >= 1 && K >= 1 && K <= 31) ? PoiMfma::floats(N, K) : 0; }
+
+hipError_t run_poisson_pack(const ModelArgs& m, float* xp, hipStream_t s) {
+  if (m.k < 1 || m.k > 31 || m.n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(poisson_pack_kernel, dim3((unsigned)PoiMfma::tiles(m.n)), dim3(256), 0, s, m.data, m.n, (int)m.k,
+                     xp);
+  return hipGetLastError();
+}
+
+static hipError_t run_poisson_potential(const PotParams& p, hipStream_t s) {
+  if (p.xpack == nullptr || p.model.k != p.d - 1 || p.model.n < 1) return hipErrorInvalidValue;
+  constexpr int per_block = 4 * 32 * kLogNB;
+  const dim3 grid((unsigned)((p.n + per_block - 1) / per_block));
+  switch (PoiMfma::gv(p.model.k)) {
+    case 1:
+      hipLaunchKernelGGL(poisson_pot_mfma_kernel<1>, grid, dim3(256), 0, s, p);
+      break;
+    case 2:
+      hipLaunchKernelGGL(poisson_pot_mfma_kernel<2>, grid, dim3(256), 0, s, p);
+      break;
+    case 3:
+      hipLaunchKernelGGL(poisson_pot_mfma_kernel<3>, grid, dim3(256), 0, s, p);
+      break;
+    default:
+      hipLaunchKernelGGL(poisson_pot_mfma_kernel<4>, grid, dim3(256), 0, s, p);
+      break;
+  }
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- launchers --
 hipError_t run_propose(const StepParams& p, float* xprop, hipStream_t s) {
   if (p.d < 1 || p.d > 64) return hipErrorInvalidValue;
@@ -602,6 +785,7 @@ hipError_t run_propose(const StepParams& p, float* xprop, hipStream_t s) {
 hipError_t run_potential_lane(int model_id, const PotParams& p, hipStream_t s) {
   if (!split_model(model_id, p.d)) return hipErrorInvalidValue;
   if (model_id == AMH_MODEL_LOGISTIC) return run_logistic_potential(p, s);
+  if (model_id == AMH_MODEL_POISSON) return run_poisson_potential(p, s);
   if (p.xpack != nullptr && p.model.k - 1 == kDiaMfmaKc && p.d == kDiaMfmaKc + 2) {
     constexpr int per_block = 4 * 32 * kDiaNB;
     hipLaunchKernelGGL((diamonds_pot_mfma_kernel<kDiaMfmaKc, kDiaNB>), dim3((unsigned)((p.n + per_block - 1) / per_block)),

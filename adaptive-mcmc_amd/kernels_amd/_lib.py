@@ -24,6 +24,7 @@ AMH_MODEL_DIAMONDS_SS = 5
 AMH_MODEL_MIXTURE = 6
 AMH_MODEL_EXTERNAL = 7  # the caller's potential (amh_propose / amh_step_external)
 AMH_MODEL_LOGISTIC = 8  # logistic regression on the caller's data (posteriors.logistic_regression)
+AMH_MODEL_POISSON = 9  # Poisson regression on the caller's data (posteriors.poisson_regression)
 AMH_STEP_PROPOSAL_READY = 1
 AMH_STEP_KEEP_PROPOSAL = 2
 AMH_ASSS_EXT_ROUNDS = 51  # shrink rounds 0 .. 50 of the external slice sampler (amh_asss_ext_shrink)

@@ -354,12 +354,12 @@ class ARWMH:
     def _chained_path(self) -> bool:
         """Paths whose step pass forms the next transition's proposal: d > 64
         (amh_big.hip) and the split transition of the literal diamonds model
-        and of logistic regression (amh_split.hip; include/amh.h
+        and of logistic and Poisson regression (amh_split.hip; include/amh.h
         AMH_STEP_KEEP_PROPOSAL)."""
         if self._dim > 64:
             return True
         mid = self._model.model_id if self._model is not None else self._potential_fn.model_id
-        if mid == _lib.AMH_MODEL_LOGISTIC:  # always split (2 <= d <= 32)
+        if mid in (_lib.AMH_MODEL_LOGISTIC, _lib.AMH_MODEL_POISSON):  # always split (2 <= d <= 32)
             return True
         return mid == _lib.AMH_MODEL_DIAMONDS and 3 <= self._dim <= 32
 

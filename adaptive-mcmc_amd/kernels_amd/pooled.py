@@ -314,7 +314,7 @@ class PooledARWMH(ARWMH):
                 cur.z, cur.potential_energy = sout.z.data_ptr(), sout.potential_energy.data_ptr()
 
     def _step_order_block(self) -> bool:
-        """Logistic regression at sync_every > 1: the block runs as K
+        """Logistic and Poisson regression at sync_every > 1: the block runs as K
         single-step stats launches whose completely reduced sums are added in
         step order -- the callable path's association (include/amh.h,
         amh_pooled_stats_external), so PooledARWMH(model=entry) equals
@@ -322,7 +322,7 @@ class PooledARWMH(ARWMH):
         sync_every.  The other registry models keep the one-launch block, whose
         sums are associated inside the chunk."""
         return self.sync_every > 1 and self._model is not None and \
-            self._model.model_id == _lib.AMH_MODEL_LOGISTIC
+            self._model.model_id in (_lib.AMH_MODEL_LOGISTIC, _lib.AMH_MODEL_POISSON)
 
     def _stats_step_order(self, L, cin, sout, b, C):
         dev = sout.z.device

@@ -59,7 +59,7 @@ class PooledASSS(PooledARWMH):
     host_shrink=True (the fused slice transition evaluates the potential
     inside the kernel), and host_shrink=True needs a callable; no
     exact_sums; not the logistic_regression model (the pooled slice kernel has
-    no instantiation for it)."""
+    no instantiation for it; poisson_regression has one)."""
 
     def __init__(self, model=None, potential_fn=None, lr_decay=2 / 3, eps=1e-6, num_chains=None, device=None,
                  chain_offset=0, group=None, sync_every: int = 1, overlap: bool = False, exact_sums: bool = False,

@@ -11,8 +11,9 @@ Python callable, so each model here is a registry entry that knows
 
 Entries: eight_schools (non-centred), kidiq_kidscore_momhsiq, diamonds, a
 dense Gaussian potential (the build's benchmark targets), the notebook's
-normal mixture potential (asumptions_check.ipynb cells 61-62) and logistic
-regression on the caller's own data (logistic_regression(X, y)).
+normal mixture potential (asumptions_check.ipynb cells 61-62), and logistic
+and Poisson regression on the caller's own data (logistic_regression(X, y),
+poisson_regression(X, y, offset)).
 """
 from __future__ import annotations
 
@@ -294,6 +295,126 @@ def synthetic_logistic(N: int = 5000, K: int = 24, seed: int = 8) -> dict:
     p = 1.0 / (1.0 + np.exp(-(0.5 + X.astype(np.float64) @ b)))
     y = (rng.random(N) < p).astype(np.float32)
     return {"X": X, "y": y}
+
+
+# -------------------------------------------------------- Poisson regression --
+# The second data-carrying model (include/amh.h AMH_MODEL_POISSON): counts with
+# a log link and an optional per-row offset.
+class PoissonRegression(Model):
+    """Bayesian Poisson regression on the caller's data: y_n ~ Poisson(exp(
+    Intercept + X_n b + offset_n)), Intercept ~ N(0, intercept_scale), b_k ~
+    N(0, prior_scale).  Shaped like `LogisticRegression`: it carries its data,
+    `model_kwargs` stays empty and every method's `data` argument is ignored."""
+
+    def __init__(self, X: np.ndarray, y: np.ndarray, offset: np.ndarray, prior_scale: float, intercept_scale: float):
+        self.X, self.y, self.offset = X, y, offset  # float32, as the device reads them
+        self.N, self.K = X.shape
+        self.prior_scale, self.intercept_scale = float(prior_scale), float(intercept_scale)
+        sI, sb = self.intercept_scale, self.prior_scale
+        # iI2, ib2, c0 (with sum_n lgamma(y_n + 1): U is the full -log joint):
+        # float64 on the host, then rounded once
+        lg = math.fsum(math.lgamma(float(v) + 1.0) for v in y)
+        self.consts = np.array([1.0 / (sI * sI), 1.0 / (sb * sb),
+                                math.log(sI * math.sqrt(2.0 * math.pi)) +
+                                self.K * math.log(sb * math.sqrt(2.0 * math.pi)) + lg], np.float64).astype(np.float32)
+        super().__init__("poisson_regression", _lib.AMH_MODEL_POISSON, self._sites, self._pack, None,
+                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Poisson(exp(Intercept + X b + offset))")
+
+    def _sites(self, data=None):
+        return [Site("Intercept", 1), Site("b", self.K)]
+
+    def _pack(self, data=None):
+        return np.concatenate([self.X.reshape(-1), self.y, self.offset, self.consts]), (self.N, self.K)
+
+    def sites(self, data: dict = None) -> List[Site]:
+        return self._sites()
+
+    def dim(self, data: dict = None) -> int:
+        return self.K + 1
+
+    def pack(self, data: dict = None, device="cpu") -> Tuple[torch.Tensor, Tuple[int, ...]]:
+        return super().pack(data, device)
+
+    def unravel(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
+        # b keeps its axis at K = 1 (a Site of size 1 would lose it)
+        return {"Intercept": z[..., 0], "b": z[..., 1:self.K + 1]}
+
+    def postprocess(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
+        return self.unravel(z)
+
+
+def poisson_regression(X, y, offset=None, prior_scale: float = 2.5,
+                       intercept_scale: float = 10.0) -> PoissonRegression:
+    """Registry entry for ARWMH / ASSS / PooledARWMH / PooledASSS(model=...) and
+    MCMC, with X [N, K] (1 <= K <= 31, no intercept column: the model has its
+    own), counts y [N] (non-negative integers up to 2^24) and an optional
+    offset [N] (log exposure); the data travel with the entry (init's
+    model_kwargs = {})."""
+    Xa = np.asarray(_np(X))
+    if Xa.ndim != 2:
+        raise ValueError(f"X must be 2-D [N, K], not {Xa.ndim}-D")
+    N, K = Xa.shape
+    if N < 1:
+        raise ValueError("X needs at least one row")
+    if not 1 <= K <= 31:
+        raise ValueError(f"poisson_regression supports 1 <= K <= 31 predictors, not K = {K}")
+    with np.errstate(over="ignore"):  # a value past float32 becomes inf and is refused below
+        Xa = np.ascontiguousarray(Xa, dtype=np.float32)
+    if not np.all(np.isfinite(Xa)):
+        raise ValueError("X must be finite (in float32)")
+    ya = np.asarray(_np(y)).reshape(-1).astype(np.float64)
+    if ya.shape[0] != N:
+        raise ValueError(f"y has {ya.shape[0]} entries for {N} rows of X")
+    if not np.all((ya >= 0) & (ya <= 2.0 ** 24) & (ya == np.floor(ya))):  # NaN fails every comparison
+        raise ValueError("every y must be a non-negative integer, at most 2^24")
+    if offset is None:
+        oa = np.zeros(N, np.float32)
+    else:
+        oa = np.asarray(_np(offset)).reshape(-1)
+        if oa.shape[0] != N:
+            raise ValueError(f"offset has {oa.shape[0]} entries for {N} rows of X")
+        with np.errstate(over="ignore"):
+            oa = np.ascontiguousarray(oa, dtype=np.float32)
+        if not np.all(np.isfinite(oa)):
+            raise ValueError("offset must be finite (in float32)")
+    if not (float(prior_scale) > 0 and math.isfinite(float(prior_scale))):
+        raise ValueError("prior_scale must be positive")
+    if not (float(intercept_scale) > 0 and math.isfinite(float(intercept_scale))):
+        raise ValueError("intercept_scale must be positive")
+    return PoissonRegression(Xa, ya.astype(np.float32), oa, prior_scale, intercept_scale)
+
+
+def poisson_potential_f64(z, entry: PoissonRegression) -> torch.Tensor:
+    """U of `entry` in float64 on the float32 data and constants the device
+    reads: sum_n [exp(eta_n) - y_n eta_n] + b'b ib2 / 2 + I^2 iI2 / 2 + c0 with
+    eta_n = I + X_n b + o_n, for z [..., K + 1] (a torch tensor on any device,
+    or an array)."""
+    z = torch.as_tensor(z).to(torch.float64)
+    dev = z.device
+    X = torch.as_tensor(entry.X, device=dev).to(torch.float64)
+    y = torch.as_tensor(entry.y, device=dev).to(torch.float64)
+    o = torch.as_tensor(entry.offset, device=dev).to(torch.float64)
+    iI2, ib2, c0 = (float(v) for v in entry.consts)
+    icpt, b = z[..., 0], z[..., 1:]
+    eta = icpt[..., None] + b @ X.T + o
+    t = torch.exp(eta) - y * eta
+    return t.sum(-1) + 0.5 * (b * b).sum(-1) * ib2 + 0.5 * icpt * icpt * iI2 + c0
+
+
+def synthetic_poisson(N: int = 5000, K: int = 24, seed: int = 9) -> dict:
+    """Synthetic Poisson-regression data: standard normal predictors with
+    pairwise correlation 0.3, offsets uniform in [-1, 1], y ~ Poisson(exp(0.5 +
+    X b* + o)) with b* ~ N(0, 0.5 / sqrt(K)), so that eta has a standard
+    deviation of about 0.8 around 0.5 at any K.  Returns {"X": [N, K] float32,
+    "y": [N] float32 counts, "offset": [N] float32}."""
+    rng = np.random.default_rng(seed)
+    f = rng.normal(size=(N, 1))
+    X = (math.sqrt(0.3) * f + math.sqrt(0.7) * rng.normal(size=(N, K))).astype(np.float32)
+    b = rng.normal(0.0, 0.5 / math.sqrt(K), size=K)
+    o = rng.uniform(-1.0, 1.0, size=N).astype(np.float32)
+    eta = 0.5 + X.astype(np.float64) @ b + o.astype(np.float64)
+    y = rng.poisson(np.exp(eta)).astype(np.float32)
+    return {"X": X, "y": y, "offset": o}
 
 
 # ------------------------------------------------------------------ gaussian --

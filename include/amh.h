@@ -71,7 +71,7 @@ enum {
                                   pe0 = 0 for the caller to fill, transitions run through
                                   amh_propose / amh_step_external; data ignored (non-null,
                                   n_data >= 0, no iparams), 1 <= d <= 256 */
-  AMH_MODEL_LOGISTIC = 8       /* Bayesian logistic regression on the caller's data (no
+  AMH_MODEL_LOGISTIC = 8,      /* Bayesian logistic regression on the caller's data (no
                                   counterpart in the reference): y_n ~ Bernoulli(logit^-1(I +
                                   X_n b)), I ~ N(0, s_I), b_k ~ N(0, s_b).  z = [Intercept,
                                   b_0 .. b_{K-1}] (unconstrained = constrained), d = K + 1,
@@ -93,12 +93,41 @@ enum {
                                   amh_step / amh_init / amh_potential evaluate it on MFMA
                                   from a tile copy made by amh_bind_model.  Not accepted by
                                   amh_pooled_asss_* (AMH_EINVAL). */
+  AMH_MODEL_POISSON = 9        /* Bayesian Poisson regression with log link on the caller's
+                                  data (no counterpart in the reference): y_n ~ Poisson(exp(I
+                                  + X_n b + o_n)), I ~ N(0, s_I), b_k ~ N(0, s_b), o the
+                                  per-row offset (log exposure).  z = [Intercept, b_0 ..
+                                  b_{K-1}] (unconstrained = constrained), d = K + 1, 1 <= K
+                                  <= 31, N >= 1; iparams {N, K}; data [X (N*K, row-major) |
+                                  y (N) | o (N) | iI2, ib2, c0], n_data = N K + 2 N + 3; y
+                                  non-negative integers that float32 holds exactly (y <=
+                                  2^24), o all +0 without an offset; iI2 = 1 / s_I^2, ib2 =
+                                  1 / s_b^2, c0 = log(s_I sqrt(2 pi)) + K log(s_b sqrt(2 pi))
+                                  + sum_n lgamma(y_n + 1), so that U is the full -log joint
+                                  (host, float64, then rounded once).  Bit spec (explicit
+                                  fmaf and amh_math.h only, no contraction):
+                                    m_n   = fmaf(X[n][k], b_k, m) from m = +0, k ascending
+                                    eta_n = (I + m_n) + o_n
+                                    t_n   = amh_expf(eta_n) - (y_n * eta_n)   (the product is
+                                            rounded, then the difference)
+                                    part[n mod 32] = part[n mod 32] + t_n, from 0, in row order
+                                    S = the 32-lane xor butterfly of part (offsets 1, 2, 4, 8, 16)
+                                    B = the same butterfly of x_r^2 over r = 1 .. K (0 elsewhere)
+                                    U = ((S + (0.5 B) ib2) + (0.5 (I I)) iI2) + c0
+                                  A NaN U is +inf to every accept or slice test (the
+                                  kernels' rule); an overflowing amh_expf gives U = +inf,
+                                  which rejects: there is no guard.  Every kernel runs it at
+                                  lane-group width 32 (the pooled kernels at 64 with +0 in
+                                  the upper half, same bits); amh_step / amh_init /
+                                  amh_potential evaluate it on MFMA from a tile copy made by
+                                  amh_bind_model.  Accepted by amh_pooled_asss_*. */
 };
 
 typedef struct amh_config {
   int32_t dim;                /* d, flat unconstrained dimension: 1..64 for
                                  every model (each within its own range in
-                                 the registry above: logistic 2..32, ...);
+                                 the registry above: logistic and poisson 2..32,
+                                 ...);
                                  64 < d <= 256 for the dense
                                  Gaussian (regime A, sample_Pnx and ASSS; the
                                  pooled mode needs d % 32 == 0) */
@@ -200,7 +229,7 @@ int amh_step64_stolen(amh_handle* h, int64_t* stolen, void* stream);
 /* Model plug-in (arwmh.py:109-116 / the scripts' numpyro models).
  * data: device pointer, n_data floats; iparams model-specific:
  *   GAUSSIAN: none.  EIGHT_SCHOOLS: {J}.  KIDIQ: {N}.  DIAMONDS: {N, K}.
- *   LOGISTIC: {N, K}. */
+ *   LOGISTIC: {N, K}.  POISSON: {N, K}. */
 int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n_data,
                    const int64_t* iparams, int32_t n_iparams);
 
@@ -216,7 +245,7 @@ int amh_step(amh_handle* h, int64_t num_chains, const amh_state* in, const amh_s
              int32_t n_steps, const amh_collect* collect, void* stream);
 
 /* amh_step with flags (64 < d <= 256 and the split transition of the literal
- * diamonds model and of logistic regression; other shapes ignore them).  The step pass of those paths forms
+ * diamonds model, of logistic and of Poisson regression; other shapes ignore them).  The step pass of those paths forms
  * the next transition's proposal while it streams L' out (so the factor is
  * read once per transition); AMH_STEP_KEEP_PROPOSAL keeps the one after the last step in
  * the handle, and AMH_STEP_PROPOSAL_READY tells the next call that its `in` is
@@ -521,8 +550,8 @@ int amh_pooled_allreduce(amh_handle* h, double* sums, int64_t n, void* rccl_comm
  * With one chain in total this is the reference's recurrence (asss.py:246-255).
  * Arguments, in-place aliasing and errors as amh_pooled_stats_k / _update_k /
  * _step_k.  d <= 64 and a device potential (Gaussian, eight schools, kidiq,
- * diamonds, diamonds_suffstat): AMH_EINVAL otherwise (the logistic model has
- * no instantiation of this kernel). */
+ * diamonds, diamonds_suffstat, poisson): AMH_EINVAL otherwise (the logistic
+ * model has no instantiation of this kernel). */
 int amh_pooled_asss_stats_k(amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int32_t k_steps,
                             float* z_out, float* pe_out, double* sums, void* stream);
 int amh_pooled_asss_update_k(amh_handle* h, const double* sums, const amh_pooled_state* in,
