@@ -1089,6 +1089,76 @@ int amh_normals(const uint32_t key[2], int64_t n, float* out, void* stream) {
   return AMH_OK;
 }
 
+// linear assignment by auction (amh_assign.hip)
+int amh_assign_work_size(int64_t n, int64_t* bytes) {
+  if (!bytes || n < 1 || n > amh::kAssignMaxN)
+    return fail(nullptr, AMH_EINVAL, "amh_assign_work_size: n must be in 1 .. 65536");
+  *bytes = amh::assign_work_bytes(n);
+  return AMH_OK;
+}
+
+namespace {
+bool assign_args_ok(const void* work, int64_t n) {
+  return work && ((uintptr_t)work & 7u) == 0 && n >= 1 && n <= amh::kAssignMaxN;
+}
+}  // namespace
+
+int amh_assign_begin(const float* cost, int64_t n, void* work, void* stream) {
+  if (!cost || ((uintptr_t)cost & 3u) != 0 || !assign_args_ok(work, n))
+    return fail(nullptr, AMH_EINVAL, "amh_assign_begin: bad arguments (square float32 costs, 1 <= n <= 65536)");
+  const hipError_t e = amh::run_assign_begin(cost, n, work, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_begin");
+  return AMH_OK;
+}
+
+int amh_assign_quantum(const void* work, int64_t n, int32_t* e_out, int64_t* qmax, void* stream) {
+  if (!assign_args_ok(work, n) || !e_out || !qmax) return fail(nullptr, AMH_EINVAL, "amh_assign_quantum: bad arguments");
+  int64_t hdr[amh::kAssignHdrWords];
+  const hipError_t e = amh::run_assign_header(work, hdr, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_quantum");
+  if (hdr[1] != 0)
+    return fail(nullptr, AMH_EINVAL, "amh_assign_quantum: the cost matrix holds a NaN, an infinity or a negative entry");
+  *e_out = (int32_t)hdr[2];
+  *qmax = hdr[3];
+  return AMH_OK;
+}
+
+int amh_assign_phase(void* work, int64_t n, void* stream) {
+  if (!assign_args_ok(work, n)) return fail(nullptr, AMH_EINVAL, "amh_assign_phase: bad arguments");
+  const hipError_t e = amh::run_assign_phase(work, n, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_phase");
+  return AMH_OK;
+}
+
+int amh_assign_rounds(const float* cost, int64_t n, void* work, int64_t eps, int64_t bound, int64_t first,
+                      int32_t rounds, void* stream) {
+  if (!cost || ((uintptr_t)cost & 3u) != 0 || !assign_args_ok(work, n) || eps < 1 || bound < 1 || bound > n ||
+      first < 0 || rounds < 0 || rounds > 65536)
+    return fail(nullptr, AMH_EINVAL, "amh_assign_rounds: bad arguments");
+  const hipError_t e = amh::run_assign_rounds(cost, n, work, eps, bound, first, rounds, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_rounds");
+  return AMH_OK;
+}
+
+int amh_assign_status(const void* work, int64_t n, int64_t queued, int64_t* unassigned, int64_t* rounds,
+                      void* stream) {
+  if (!assign_args_ok(work, n) || queued < 0 || !unassigned || !rounds)
+    return fail(nullptr, AMH_EINVAL, "amh_assign_status: bad arguments");
+  int64_t hdr[amh::kAssignHdrWords];
+  const hipError_t e = amh::run_assign_header(work, hdr, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_status");
+  *unassigned = hdr[5 + (queued & 1)];
+  *rounds = hdr[4];
+  return AMH_OK;
+}
+
+int amh_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price, void* stream) {
+  if (!assign_args_ok(work, n) || (!perm && !price)) return fail(nullptr, AMH_EINVAL, "amh_assign_result: bad arguments");
+  const hipError_t e = amh::run_assign_result(work, n, perm, price, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_assign_result");
+  return AMH_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------- pooled covariance --

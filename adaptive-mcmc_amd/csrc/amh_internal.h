@@ -296,6 +296,21 @@ hipError_t run_kernel_sum(const float* A, int64_t n, const float* B, int64_t m, 
                           double* partials, double* out, hipStream_t s);
 hipError_t run_dist2(const float* A, int64_t n, const float* B, int64_t m, int d, float* out, hipStream_t s);
 hipError_t run_normals(uint32_t k0, uint32_t k1, int64_t n, float* out, hipStream_t s);
+// linear assignment by auction (amh_assign.hip); the work buffer opens with
+// kAssignHdrWords int64 words: cmax bits, refusal flag, e, qmax, rounds run,
+// the two list counts, one spare
+constexpr int kAssignHdrWords = 8;
+constexpr int64_t kAssignMaxN = 65536;
+int64_t assign_work_bytes(int64_t n);
+hipError_t run_assign_begin(const float* cost, int64_t n, void* work, hipStream_t s);
+hipError_t run_assign_phase(void* work, int64_t n, hipStream_t s);
+// `rounds` rounds (bid, claim, award) over at most `bound` unassigned persons,
+// `first` rounds having been queued since run_assign_phase
+hipError_t run_assign_rounds(const float* cost, int64_t n, void* work, int64_t eps, int64_t bound, int64_t first,
+                             int32_t rounds, hipStream_t s);
+// the header to host memory; waits for the stream
+hipError_t run_assign_header(const void* work, int64_t* host8, hipStream_t s);
+hipError_t run_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price, hipStream_t s);
 // asss: the pooled ASSS update (log_step_size copied through, as_change of asss.py:259-260)
 hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s, bool asss = false);
 // pooled ASSS (amh_pooled_asss.hip): the slice transition against the shared

@@ -95,6 +95,14 @@ def _signatures():
         "amh_pairwise_dist2": (I, [P, I64, P, I64, I32, P, P]),
         "amh_normals": (I, [KEY, I64, P, P]),
         "amh_sinkhorn_lse": (I, [P, I64, I64, P, F, F, P, P]),
+        # linear assignment (auction)
+        "amh_assign_work_size": (I, [I64, ctypes.POINTER(I64)]),
+        "amh_assign_begin": (I, [P, I64, P, P]),
+        "amh_assign_quantum": (I, [P, I64, ctypes.POINTER(I32), ctypes.POINTER(I64), P]),
+        "amh_assign_phase": (I, [P, I64, P]),
+        "amh_assign_rounds": (I, [P, I64, P, I64, I64, I64, I32, P]),
+        "amh_assign_status": (I, [P, I64, I64, ctypes.POINTER(I64), ctypes.POINTER(I64), P]),
+        "amh_assign_result": (I, [P, I64, P, P, P]),
         # pooled covariance
         "amh_pooled_sums_size": (I, [I32, ctypes.POINTER(I64)]),
         "amh_pooled_stats": (I, [P, I64, PS, P, P, P, P]),

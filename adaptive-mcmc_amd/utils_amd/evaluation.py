@@ -5,7 +5,17 @@ GPU, same function names and arguments.
   wasserstein_dist11_p     evaluation.py:43-67    optimal 1-1 coupling; the
                                                    reference runs scipy's
                                                    Hungarian on the host, and
-                                                   so does this one
+                                                   so does method="hungarian"
+                                                   (the default);
+                                                   method="auction" builds the
+                                                   cost matrix and solves the
+                                                   assignment on the device
+  linear_assignment        (no reference analogue) square assignment problem by
+                                                   an integer auction with
+                                                   epsilon-scaling in HIP
+                                                   (amh_assign_*): within 2
+                                                   quanta (each <= 2^-29 x the
+                                                   largest cost) of the optimum
   wasserstein_1d           evaluation.py:139-162  sorted differences (device)
   max_sliced_wasserstein   evaluation.py:165-206  projections = one GEMM
                                                    (hipBLASLt through torch),
@@ -55,6 +65,7 @@ with the reference in distribution, not bit for bit.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
@@ -63,8 +74,8 @@ import torch
 from kernels_amd import _lib
 from kernels_amd.random import as_key
 
-__all__ = ["pth_moment_rmse", "wasserstein_dist11_p", "wasserstein_1d", "max_sliced_wasserstein", "gaussian_kernel",
-           "mmd2_unbiased", "mmd_heuristic", "wasserstein_sinkhorn", "wasserstein_sinkhorn_unbiased"]
+__all__ = ["pth_moment_rmse", "wasserstein_dist11_p", "linear_assignment", "wasserstein_1d", "max_sliced_wasserstein",
+           "gaussian_kernel", "mmd2_unbiased", "mmd_heuristic", "wasserstein_sinkhorn", "wasserstein_sinkhorn_unbiased"]
 
 
 def _dev(x) -> torch.Tensor:
@@ -108,8 +119,106 @@ def pth_moment_rmse(x, y, p=2.0) -> float:
     return float(torch.linalg.vector_norm(torch.mean(x ** p, dim=0) - torch.mean(y ** p, dim=0)))
 
 
-def wasserstein_dist11_p(u_values, v_values, ord=2.0) -> float:
-    """Optimal 1-1 coupling cost (evaluation.py:43-67; host, as the reference)."""
+ASSIGN_THETA = 4       # epsilon-scaling factor of linear_assignment (DESIGN.md §8 holds the sweep)
+ASSIGN_BATCH = 64      # rounds queued between two reads of the unassigned count
+ASSIGN_MAX_N = 65536
+ASSIGN_MAX_ROUNDS = None  # the default cap on rounds; None: 64 n + 4096
+
+
+def linear_assignment(cost, *, theta=None, max_rounds=None) -> dict:
+    """Minimum-cost perfect matching of a square device cost matrix [n][n]
+    (float32, finite, >= 0; 1 <= n <= 65536) by the integer auction of
+    csrc/amh_assign.hip: costs quantised to quantum = 2^e <= cmax 2^-29,
+    epsilon-scaling by `theta` (default ASSIGN_THETA) down to epsilon = 1.
+    The matching's mean cost exceeds the optimum's by at most 2 quantum.
+
+    Returns dict(perm: device int64 person -> object, cost: mean of the
+    caller's costs along perm (float64 sum), rounds, phases, quantum, e,
+    price: device int64 final prices, converged).  `max_rounds` (default
+    64 n + 4096) caps the rounds; when it runs out, converged is False and
+    perm holds -1 for the persons left unassigned."""
+    if not isinstance(cost, torch.Tensor):
+        raise TypeError("linear_assignment takes a torch tensor on the device")
+    if cost.dim() != 2 or cost.shape[0] != cost.shape[1] or cost.shape[0] < 1:
+        raise ValueError(f"linear_assignment needs a square cost matrix, got {tuple(cost.shape)}")
+    n = int(cost.shape[0])
+    if n > ASSIGN_MAX_N:
+        raise ValueError(f"linear_assignment: n = {n} exceeds {ASSIGN_MAX_N}")
+    theta = ASSIGN_THETA if theta is None else int(theta)
+    if theta < 2:
+        raise ValueError("theta must be an integer >= 2")
+    if max_rounds is None:
+        max_rounds = 64 * n + 4096 if ASSIGN_MAX_ROUNDS is None else ASSIGN_MAX_ROUNDS
+    max_rounds = int(max_rounds)
+    if max_rounds < 0:
+        raise ValueError("max_rounds must be >= 0")
+    _lib.require_gpu(cost)
+    cost = cost.detach().to(torch.float32).contiguous()
+    L = _lib.lib()
+    dev = cost.device
+    nbytes = ctypes.c_int64()
+    _lib.check(L.amh_assign_work_size(n, ctypes.byref(nbytes)))
+    work = torch.empty(nbytes.value // 8, dtype=torch.int64, device=dev)
+    perm = torch.empty(n, dtype=torch.int64, device=dev)
+    price = torch.empty(n, dtype=torch.int64, device=dev)
+    e, qmax = ctypes.c_int32(), ctypes.c_int64()
+    left, done = ctypes.c_int64(), ctypes.c_int64()
+    with torch.cuda.device(dev.index):
+        s = _stream(cost)
+        _lib.check(L.amh_assign_begin(_lib.ptr(cost), n, _lib.ptr(work), s))
+        if L.amh_assign_quantum(_lib.ptr(work), n, ctypes.byref(e), ctypes.byref(qmax), s) != 0:
+            raise ValueError(L.amh_last_error(None).decode())
+        eps = max(1, qmax.value // 2)
+        rounds = phases = 0
+        converged = True
+        while True:
+            phases += 1
+            _lib.check(L.amh_assign_phase(_lib.ptr(work), n, s))
+            bound, queued = n, 0
+            while bound > 0:
+                batch = min(ASSIGN_BATCH, max_rounds - rounds)
+                if batch == 0:
+                    converged = False
+                    break
+                _lib.check(L.amh_assign_rounds(_lib.ptr(cost), n, _lib.ptr(work), eps, bound, queued, batch, s))
+                queued += batch
+                _lib.check(L.amh_assign_status(_lib.ptr(work), n, queued, ctypes.byref(left), ctypes.byref(done), s))
+                bound, rounds = left.value, done.value
+            if not converged or eps == 1:
+                break
+            eps = max(1, eps // theta)
+        _lib.check(L.amh_assign_result(_lib.ptr(work), n, _lib.ptr(perm), _lib.ptr(price), s))
+        mean = float("nan")
+        if converged:
+            mean = float(cost.gather(1, perm[:, None]).double().sum().item()) / n
+    return dict(perm=perm, cost=mean, rounds=rounds, phases=phases, quantum=math.ldexp(1.0, e.value) if qmax.value else 0.0,
+                e=e.value, price=price, converged=converged)
+
+
+def _wasserstein_auction(u_values, v_values, ord) -> float:
+    nu, nv = len(u_values), len(v_values)
+    if nu != nv:
+        raise ValueError(f'method="auction" needs equally many samples, got {nu} and {nv}')
+    u, v = _dev(u_values), _dev(v_values)
+    if float(ord) == 2.0:
+        cost = _dist2(u, v).clamp_(min=0.0).sqrt_()
+    else:
+        cost = torch.cdist(u, v, p=float(ord))
+    res = linear_assignment(cost)
+    if not res["converged"]:
+        raise RuntimeError(f"linear_assignment: no matching within {res['rounds']} rounds (n = {nu})")
+    return res["cost"]
+
+
+def wasserstein_dist11_p(u_values, v_values, ord=2.0, method="hungarian") -> float:
+    """Optimal 1-1 coupling cost (evaluation.py:43-67).  method="hungarian":
+    scipy's Hungarian algorithm on the host in float64, as the reference.
+    method="auction": cost matrix and matching on the device
+    (linear_assignment; float32 costs, within 2 quantum of their optimum)."""
+    if method == "auction":
+        return _wasserstein_auction(u_values, v_values, ord)
+    if method != "hungarian":
+        raise ValueError(f'method must be "hungarian" or "auction", got {method!r}')
     from scipy.optimize import linear_sum_assignment
     from scipy.spatial import distance_matrix
     u = np.asarray(u_values.cpu() if hasattr(u_values, "cpu") else u_values)

@@ -415,6 +415,42 @@ int amh_normals(const uint32_t key[2], int64_t n, float* out, void* stream);
 int amh_pairwise_dist2(const float* a, int64_t n, const float* b, int64_t m, int32_t d, float* out,
                        void* stream);
 
+/* Linear assignment of a square cost matrix (the optimal 1-1 coupling of
+ * wasserstein_dist11_p, evaluation.py:43-67) on the device: the forward
+ * auction, Jacobi form, with epsilon-scaling, on costs quantised to the
+ * quantum 2^e (DESIGN.md §8 is the bit spec; all integers, so the result does
+ * not depend on launch geometry).  cost: row-major [n][n] device float32,
+ * 1 <= n <= 65536, every entry finite and >= 0; work: amh_assign_work_size
+ * bytes of device memory, 8-byte aligned, that the caller keeps from begin to
+ * result.  Nothing is kept in the library: the caller passes the same cost,
+ * n and work to every call of one solve.
+ *   amh_assign_begin    queues the scan (maximum, refusal flag) and zeroes
+ *                       the prices
+ *   amh_assign_quantum  waits; AMH_EINVAL if an entry is a NaN, an infinity or
+ *                       negative, else e and qmax = the largest quantised
+ *                       cost.  The phases run at eps_1 = max(1, qmax / 2),
+ *                       eps_{k+1} = max(1, eps_k / theta), the last at eps = 1
+ *   amh_assign_phase    every person unassigned, prices kept
+ *   amh_assign_rounds   queues `rounds` rounds (three launches each) for at
+ *                       most `bound` unassigned persons -- the count that
+ *                       amh_assign_status last returned in this phase, n at its
+ *                       start; `first`: rounds queued since amh_assign_phase.
+ *                       A round that finds nobody unassigned does nothing
+ *   amh_assign_status   waits; the unassigned count after the `queued` rounds
+ *                       queued in this phase, and the rounds that did work
+ *                       since amh_assign_begin
+ *   amh_assign_result   perm [n] (person -> object, -1 if unassigned) and / or
+ *                       the prices [n], device int64 */
+int amh_assign_work_size(int64_t n, int64_t* bytes);
+int amh_assign_begin(const float* cost, int64_t n, void* work, void* stream);
+int amh_assign_quantum(const void* work, int64_t n, int32_t* e, int64_t* qmax, void* stream);
+int amh_assign_phase(void* work, int64_t n, void* stream);
+int amh_assign_rounds(const float* cost, int64_t n, void* work, int64_t eps, int64_t bound, int64_t first,
+                      int32_t rounds, void* stream);
+int amh_assign_status(const void* work, int64_t n, int64_t queued, int64_t* unassigned, int64_t* rounds,
+                      void* stream);
+int amh_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price, void* stream);
+
 /* ---------------------------------------------------- pooled covariance ----
  * Regime B (build-defined, no reference analogue): every chain
  * proposes with ONE shared adapt state, and the adaptation of arwmh.py:180-197
