@@ -1159,6 +1159,25 @@ int amh_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price
   return AMH_OK;
 }
 
+// streaming posterior summaries (amh_summary.hip)
+int amh_summary_update(const float* x, int64_t num_draws, int64_t num_chains, int32_t num_cols, const float* calib,
+                       int32_t nbins, int64_t batch, int64_t n_before, double* acc, int64_t* hist, void* stream) {
+  if (!x || !calib || !acc || !hist || ((uintptr_t)x & 3u) != 0 || ((uintptr_t)calib & 3u) != 0 ||
+      ((uintptr_t)acc & 7u) != 0 || ((uintptr_t)hist & 7u) != 0)
+    return fail(nullptr, AMH_EINVAL, "amh_summary_update: null or misaligned buffer");
+  if (num_draws < 1 || num_chains < 1 || num_cols < 1 || num_cols > 1024)
+    return fail(nullptr, AMH_EINVAL, "amh_summary_update: num_draws >= 1, num_chains >= 1, 1 <= num_cols <= 1024");
+  if (nbins < 64 || nbins > 2048 || (nbins & (nbins - 1)) != 0)
+    return fail(nullptr, AMH_EINVAL, "amh_summary_update: nbins must be a power of two in 64 .. 2048");
+  if (batch < 1 || n_before < 0) return fail(nullptr, AMH_EINVAL, "amh_summary_update: batch >= 1, n_before >= 0");
+  if (num_draws > INT64_MAX / num_chains / num_cols)
+    return fail(nullptr, AMH_EINVAL, "amh_summary_update: the block's element count overflows int64");
+  const hipError_t e = amh::run_summary_update(x, num_draws, num_chains, num_cols, calib, nbins, batch, n_before, acc,
+                                               hist, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "amh_summary_update");
+  return AMH_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------- pooled covariance --

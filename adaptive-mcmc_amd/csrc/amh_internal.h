@@ -311,6 +311,10 @@ hipError_t run_assign_rounds(const float* cost, int64_t n, void* work, int64_t e
 // the header to host memory; waits for the stream
 hipError_t run_assign_header(const void* work, int64_t* host8, hipStream_t s);
 hipError_t run_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price, hipStream_t s);
+// streaming summaries (amh_summary.hip): folds x [B][C][k] into acc [5][C][k]
+// and hist [k][nbins + 3]; calib [3][k] = center, lo, inv_w
+hipError_t run_summary_update(const float* x, int64_t B, int64_t C, int k, const float* calib, int nbins,
+                              int64_t batch, int64_t n_before, double* acc, int64_t* hist, hipStream_t s);
 // asss: the pooled ASSS update (log_step_size copied through, as_change of asss.py:259-260)
 hipError_t run_pooled_update(const PooledUpdateParams& p, hipStream_t s, bool asss = false);
 // pooled ASSS (amh_pooled_asss.hip): the slice transition against the shared

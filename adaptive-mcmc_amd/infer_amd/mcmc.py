@@ -18,15 +18,26 @@ thinning-long fused launch.  Both launch partitions are bit-reproducible
 (each equals the oracle run with the same partition); they differ from each
 other at ULP level, because a fused launch carries the factor in unit-lower
 form between its steps.
+
+run(summary_only=True) keeps no draws: after warmup the kept draws are
+produced block by block (sampler.run of summary_block draws at a time),
+constrained, flattened to columns in site order and folded into a
+`StreamingSummary` (infer_amd/streaming.py), whose memory does not grow with
+num_samples.  Blocked launches are one more launch partition: bit-reproducible,
+equal to the oracle run with the same partition, and different at ULP level
+from the one fused launch of the default mode for the reason above.
 """
 from __future__ import annotations
 
+import math
+from itertools import product
 from operator import attrgetter
 from typing import Dict, Sequence
 
 import torch
 
 from . import diagnostics
+from .streaming import StreamingSummary, format_streaming_summary
 
 __all__ = ["MCMC"]
 
@@ -82,6 +93,8 @@ class MCMC:
         self._last_state = None
         self._warmup_state = None
         self._args = ((), {})
+        self.streaming_summary = None  # run(summary_only=True)
+        self._summary_cols = None  # [(site or None, trailing shape, first column)]
 
     # ------------------------------------------------------------ properties --
     @property
@@ -121,18 +134,100 @@ class MCMC:
         self._last_state = state
         return state
 
-    def run(self, rng_key, *args, extra_fields: Sequence[str] = (), init_params=None, **kwargs):
+    def run(self, rng_key, *args, extra_fields: Sequence[str] = (), init_params=None, summary_only: bool = False,
+            summary_batch=None, summary_block=None, **kwargs):
         """Warmup (unless post_warmup_state is set) then num_samples steps,
-        recording every thinning-th state."""
+        recording every thinning-th state.
+
+        summary_only=True stores no draws: every thinning-th state goes,
+        summary_block draws at a time, through the postprocess_fn into
+        `self.streaming_summary` (batch length summary_batch, default
+        floor(sqrt(num_samples // thinning)); block default: the largest with
+        4 B C k <= 256 MiB).  The first block calibrates the histogram.
+        get_samples() then raises; print_summary() prints the same table from
+        the running statistics.  The blocked launches are a launch partition
+        of their own (module docstring): draws differ at ULP level from the
+        default mode's one fused launch."""
+        if summary_only and tuple(extra_fields):
+            raise ValueError("summary_only keeps no draws: extra_fields cannot be collected")
+        if not summary_only and (summary_batch is not None or summary_block is not None):
+            raise ValueError("summary_batch / summary_block need summary_only=True")
+        if summary_batch is not None and int(summary_batch) < 1:
+            raise ValueError("summary_batch must be >= 1")
+        if summary_block is not None and int(summary_block) < 1:
+            raise ValueError("summary_block must be >= 1")
         if self._warmup_state is not None:
             state = _tmap(torch.clone, self._warmup_state)
         else:
             state = self._init(rng_key, args, kwargs, init_params)
             self.sampler.sample_(state, self.num_warmup)
             self._warmup_state = _tmap(torch.clone, state)
-        state, self._states = self._collect(state, self.num_samples, self.thinning, extra_fields)
+        if summary_only:
+            self._states = None
+            state = self._stream(state, self.num_samples, self.thinning, summary_batch, summary_block)
+        else:
+            self.streaming_summary = None
+            state, self._states = self._collect(state, self.num_samples, self.thinning, extra_fields)
         self._last_state = state
         return None
+
+    def _columns(self, block):
+        """A block of draws z [B, C, d] -> ([B, C, k] float32 contiguous,
+        [(site, trailing shape, first column)]): the constrained (and
+        deterministic) sites flattened to columns in site order."""
+        fn = self.postprocess_fn
+        if fn is None:
+            fn = self.sampler.postprocess_fn(*self._args)
+        sites = fn(block)
+        if not isinstance(sites, dict):
+            return sites.to(torch.float32).contiguous(), [(None, tuple(sites.shape[2:]), 0)]
+        cols, parts, at = [], [], 0
+        for name, v in sites.items():
+            flat = v.reshape(v.shape[0], v.shape[1], -1)
+            cols.append((name, tuple(v.shape[2:]), at))
+            parts.append(flat)
+            at += flat.shape[2]
+        return torch.cat(parts, dim=2).to(torch.float32).contiguous(), cols
+
+    def _stream(self, state, n: int, thinning: int, batch, block):
+        s = self.sampler
+        rem, keep = n % thinning, n // thinning
+        if rem:
+            s.sample_(state, rem)
+        C = int(state.z.shape[0])
+        if batch is None:
+            batch = max(1, math.isqrt(keep))
+        self.streaming_summary = None
+        self._summary_cols = None
+        if keep == 0:
+            return state
+        k = int(self._columns(state.z[None])[0].shape[-1])  # the column count, from the current state
+        summ = StreamingSummary(C, k, batch=int(batch), device=state.z.device)
+        has_run = hasattr(s, "run")
+        if not has_run:
+            B = 1
+        elif block is None:
+            B = max(1, (256 << 20) // (4 * C * k))
+        else:
+            B = int(block)
+        done = 0
+        while done < keep:
+            nb = min(B, keep - done)
+            if has_run:
+                state, cz, _ = s.run(state, nb * thinning, thinning, collect_z=True, collect_pe=False)
+            else:
+                s.sample_(state, thinning)
+                cz = state.z[None]
+            x, cols = self._columns(cz)
+            del cz  # the next block's buffer reuses this one's memory
+            if done == 0:
+                summ.calibrate(x)
+                self._summary_cols = cols
+            summ.update(x)
+            del x
+            done += nb
+        self.streaming_summary = summ
+        return state
 
     def _collect(self, state, n: int, thinning: int, fields: Sequence[str]):
         s = self.sampler
@@ -182,6 +277,9 @@ class MCMC:
     # --------------------------------------------------------------- results --
     def _require(self):
         if self._states is None:
+            if self.streaming_summary is not None:
+                raise RuntimeError("no draws were kept: run(summary_only=True) keeps running statistics only "
+                                   "(see streaming_summary, print_summary)")
             raise RuntimeError("call run() first")
 
     @staticmethod
@@ -216,7 +314,29 @@ class MCMC:
             sites = {k: v for k, v in sites.items() if k in names}
         return sites
 
+    def _streaming_summary_str(self, prob: float, exclude_deterministic: bool) -> str:
+        names = None
+        model = getattr(self.sampler, "model", None)
+        if exclude_deterministic and model is not None:
+            names = {s.name for s in model.sites(self._args[1] or self.sampler._model_kwargs)}
+        labels, cols = [], []
+        for site, shp, at in self._summary_cols:
+            if site is not None and names is not None and site not in names:
+                continue
+            base = "Param:0" if site is None else site
+            if len(shp) == 0:
+                labels.append(base)
+                cols.append(at)
+            else:
+                for n_, idx in enumerate(product(*map(range, shp))):
+                    labels.append(base + "[" + ",".join(map(str, idx)) + "]")
+                    cols.append(at + n_)
+        st = self.streaming_summary.summary(probs=((1 - prob) / 2, 0.5, (1 + prob) / 2))
+        return format_streaming_summary(st, labels, prob=prob, cols=cols)
+
     def summary_str(self, prob: float = 0.9, exclude_deterministic: bool = True) -> str:
+        if self._states is None and self.streaming_summary is not None:
+            return self._streaming_summary_str(prob, exclude_deterministic)
         self._require()
         return diagnostics.format_summary(self._summary_sites(exclude_deterministic), prob=prob)
 

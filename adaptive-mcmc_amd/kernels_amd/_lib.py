@@ -103,6 +103,8 @@ def _signatures():
         "amh_assign_rounds": (I, [P, I64, P, I64, I64, I64, I32, P]),
         "amh_assign_status": (I, [P, I64, I64, ctypes.POINTER(I64), ctypes.POINTER(I64), P]),
         "amh_assign_result": (I, [P, I64, P, P, P]),
+        # streaming summaries
+        "amh_summary_update": (I, [P, I64, I64, I32, P, I32, I64, I64, P, P, P]),
         # pooled covariance
         "amh_pooled_sums_size": (I, [I32, ctypes.POINTER(I64)]),
         "amh_pooled_stats": (I, [P, I64, PS, P, P, P, P]),

@@ -451,6 +451,25 @@ int amh_assign_status(const void* work, int64_t n, int64_t queued, int64_t* unas
                       void* stream);
 int amh_assign_result(const void* work, int64_t n, int64_t* perm, int64_t* price, void* stream);
 
+/* Streaming posterior summaries (infer_amd/streaming.py; DESIGN.md §7.1 is the
+ * bit spec): folds one block of draws x [num_draws][num_chains][num_cols]
+ * (device float32, contiguous: the layout of the collect buffer of amh_step)
+ * into caller-owned running state, in one pass.  No handle; nothing is kept
+ * in the library.
+ *   calib [3][num_cols] float32: center, lo, inv_w per column
+ *   acc   [5][num_chains][num_cols] float64: S1, S2, bs, S1b, Q per (chain,
+ *         column), in draw order: y = (double)x - (double)center; S1 += y;
+ *         S2 += y*y; bs += y; when (n_before + t + 1) % batch == 0:
+ *         S1b += bs, Q += bs*bs, bs = 0.  No fma.  Non-finite draws propagate
+ *   hist  [num_cols][nbins + 3] int64, pooled over chains: t = (x - lo) * inv_w
+ *         in float32; bin nbins + 2 if t is a NaN, 0 if t < 0, nbins + 1 if
+ *         t >= nbins, else 1 + (int)t
+ * 1 <= num_cols <= 1024; nbins a power of two in 64 .. 2048; batch >= 1;
+ * n_before: the draws per chain already folded in.  acc and hist start at
+ * zero.  The result does not depend on how the draws are split into blocks. */
+int amh_summary_update(const float* x, int64_t num_draws, int64_t num_chains, int32_t num_cols, const float* calib,
+                       int32_t nbins, int64_t batch, int64_t n_before, double* acc, int64_t* hist, void* stream);
+
 /* ---------------------------------------------------- pooled covariance ----
  * Regime B (build-defined, no reference analogue): every chain
  * proposes with ONE shared adapt state, and the adaptation of arwmh.py:180-197
