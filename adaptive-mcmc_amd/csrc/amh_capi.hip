@@ -146,6 +146,20 @@ bool state_ok(const amh_state* s) {
          s->log_step_size && s->as_change && s->rng_key;
 }
 
+// a GLM's checks (amh_device.h): data = [X (N x K) | nside vectors of N | 3 prior constants]
+int glm_dim(const char* name, int nside, int64_t n_data, const int64_t* ip, int nip, std::string* why) {
+  const std::string who(name);
+  if (nip < 2) { *why = who + " needs iparams {N, K}"; return -1; }
+  const int64_t N = ip[0], K = ip[1];
+  if (K < 1 || K > 31) { *why = who + " needs 1 <= K <= 31 predictors"; return -1; }
+  if (N < 1) { *why = who + " needs N >= 1 rows"; return -1; }
+  if (n_data != N * K + nside * N + 3) {
+    *why = who + " data must hold N*K + " + (nside == 1 ? "" : std::to_string(nside) + "*") + "N + 3 floats";
+    return -1;
+  }
+  return (int)(K + 1);
+}
+
 int expected_dim(int model_id, int64_t n_data, const int64_t* ip, int nip, int d, std::string* why) {
   switch (model_id) {
     case AMH_MODEL_GAUSSIAN:
@@ -175,22 +189,10 @@ int expected_dim(int model_id, int64_t n_data, const int64_t* ip, int nip, int d
       if (n_data != 2 * (4 + 2 * Kc + Kc * Kc)) { *why = "diamonds_suffstat data must hold 2 (4 + 2 Kc + Kc^2) floats"; return -1; }
       return (int)(Kc + 2);
     }
-    case AMH_MODEL_LOGISTIC: {
-      if (nip < 2) { *why = "logistic needs iparams {N, K}"; return -1; }
-      const int64_t N = ip[0], K = ip[1];
-      if (K < 1 || K > 31) { *why = "logistic needs 1 <= K <= 31 predictors"; return -1; }
-      if (N < 1) { *why = "logistic needs N >= 1 rows"; return -1; }
-      if (n_data != N * K + N + 3) { *why = "logistic data must hold N*K + N + 3 floats"; return -1; }
-      return (int)(K + 1);
-    }
-    case AMH_MODEL_POISSON: {
-      if (nip < 2) { *why = "poisson needs iparams {N, K}"; return -1; }
-      const int64_t N = ip[0], K = ip[1];
-      if (K < 1 || K > 31) { *why = "poisson needs 1 <= K <= 31 predictors"; return -1; }
-      if (N < 1) { *why = "poisson needs N >= 1 rows"; return -1; }
-      if (n_data != N * K + 2 * N + 3) { *why = "poisson data must hold N*K + 2*N + 3 floats"; return -1; }
-      return (int)(K + 1);
-    }
+    case AMH_MODEL_LOGISTIC:
+      return glm_dim("logistic", 1, n_data, ip, nip, why);
+    case AMH_MODEL_POISSON:
+      return glm_dim("poisson", 2, n_data, ip, nip, why);
     case AMH_MODEL_MIXTURE: {
       if (nip < 1) { *why = "mixture needs iparams {K}"; return -1; }
       if (ip[0] < 1 || ip[0] > 8) { *why = "mixture needs 1 <= K <= 8 components"; return -1; }
@@ -514,21 +516,14 @@ int amh_bind_model(amh_handle* h, int32_t model_id, const float* data, int64_t n
   h->model.n = (model_id == AMH_MODEL_KIDIQ || model_id == AMH_MODEL_MIXTURE || dia) ? iparams[0] : 0;
   h->model.k = dia ? iparams[1] : 0;
   h->n_data = n_data;
-  if ((model_id == AMH_MODEL_DIAMONDS || model_id == AMH_MODEL_LOGISTIC || model_id == AMH_MODEL_POISSON) &&
-      amh::split_model(model_id, dm)) {
+  if (amh::split_model(model_id, dm)) {  // diamonds, logistic, poisson
     // the MFMA potential's tile copy of the design matrix and the response, made
     // once here (synchronous, on the null stream: the caller has synchronised the
     // stream that wrote data)
-    const bool lg = model_id == AMH_MODEL_LOGISTIC, po = model_id == AMH_MODEL_POISSON;
-    const int64_t nf = lg   ? amh::logistic_pack_floats(h->model.n, h->model.k)
-                       : po ? amh::poisson_pack_floats(h->model.n, h->model.k)
-                            : amh::diamonds_pack_floats(h->model.n, h->model.k);
+    const int64_t nf = amh::model_pack_floats(model_id, h->model.n, h->model.k);
     if (nf > 0) {
       hipError_t e = hipMalloc(&h->xpack, (size_t)nf * sizeof(float));
-      if (e == hipSuccess)
-        e = lg   ? amh::run_logistic_pack(h->model, h->xpack, nullptr)
-            : po ? amh::run_poisson_pack(h->model, h->xpack, nullptr)
-                 : amh::run_diamonds_pack(h->model, h->xpack, nullptr);
+      if (e == hipSuccess) e = amh::run_model_pack(model_id, h->model, h->xpack, nullptr);
       if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
       if (e != hipSuccess) {
         if (h->xpack) (void)hipFree(h->xpack);

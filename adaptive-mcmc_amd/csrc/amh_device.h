@@ -550,21 +550,45 @@ struct DiamondsM {
   }
 };
 
-// One row's term of the Bernoulli-logit potential (AMH_MODEL_LOGISTIC):
-// softplus(eta) - y eta, softplus as max(eta, 0) + log1p(exp(-|eta|)).  The
-// group kernel and the MFMA kernel (amh_split.hip) both call this.
+// Generalised linear models (AMH_MODEL_LOGISTIC, AMH_MODEL_POISSON).  A family
+// is the number NSIDE of per-row side vectors that follow X in the data block,
+// plus one row's term of the potential as a function of eta = I + x_n . b and
+// the row's side values.  Everything else is shared by the families and by the
+// group model below and the MFMA kernel (amh_split.hip):
+//   z = [Intercept, b (K)]; data = [X (N x K) | NSIDE vectors of N | iI2, ib2, c0]
+//   U = ((S + (0.5 B) ib2) + (0.5 I^2) iI2) + c0,  S = sum of the row terms, B = b . b
+
+// Bernoulli-logit: softplus(eta) - y eta, softplus as max(eta, 0) +
+// log1p(exp(-|eta|)).
 __device__ __forceinline__ float logistic_term(float eta, float y) {
   return (fmaxf(eta, 0.0f) + amh_log1pf(amh_expf(-fabsf(eta)))) - y * eta;
 }
 
-template <int G>
-struct LogisticM {
-  // z = [Intercept, b (K)]; data = [X (N x K) | y (N) | iI2, ib2, c0]
+// Poisson log-link: exp(eta) - y eta, the product rounded before the difference.
+__device__ __forceinline__ float poisson_term(float eta, float y) { return amh_expf(eta) - (y * eta); }
+
+struct LogisticFam {
+  static constexpr int NSIDE = 1;  // y
+  static __device__ __forceinline__ float term(float eta, const float (&sv)[NSIDE]) {
+    return logistic_term(eta, sv[0]);
+  }
+};
+
+struct PoissonFam {
+  static constexpr int NSIDE = 2;  // y, then the offset o
+  static __device__ __forceinline__ float term(float eta, const float (&sv)[NSIDE]) {
+    return poisson_term(eta + sv[1], sv[0]);
+  }
+};
+
+template <int G, class Fam>
+struct GlmM {
   // Straight VALU restatement (parity path; the data stream from L2).  The
   // bit spec has 32 partial sums whatever the group width: lane r < 32 sums
   // rows n = r, r + 32, ..., and the lanes above 32 of a G = 64 group (the
   // pooled kernels) hold +0, which the last butterfly stage adds unchanged.
-  static_assert(G >= 32, "the logistic model runs at lane-group width 32 (64 in the pooled kernels)");
+  static_assert(G >= 32, "the GLM models run at lane-group width 32 (64 in the pooled kernels)");
+  static constexpr int NSIDE = Fam::NSIDE;
   struct Ctx {
     int64_t N;
     const float* data;
@@ -576,8 +600,10 @@ struct LogisticM {
     const int64_t N = c.N;
     const int K = d - 1;
     const float* X = c.data;
-    const float* Y = X + N * K;
-    const float* pr = Y + N;  // iI2, ib2, c0
+    const float* Y = X + N * K;  // the side vectors
+    const float* sp[NSIDE];
+    static_for<NSIDE>([&](auto V) { sp[V] = Y + V * N; });
+    const float* pr = Y + NSIDE * N;  // iI2, ib2, c0
     float xb[32];
     static_for<32>([&](auto J) { xb[J] = Grp<G>::template bcast<J>(x); });
     const float icpt = xb[0];
@@ -590,7 +616,9 @@ struct LogisticM {
           if (k >= K) continue;
           m = fmaf(X[n * K + k], xb[1 + k], m);
         }
-        acc = acc + logistic_term(icpt + m, Y[n]);
+        float sv[NSIDE];  // loaded last vector first (o, then y: profiles/glm_asm_diff.txt)
+        static_for<NSIDE>([&](auto V) { sv[NSIDE - 1 - V] = sp[NSIDE - 1 - V][n]; });
+        acc = acc + Fam::term(icpt + m, sv);
       }
     }
     const float S = Grp<G>::sum(acc);
@@ -600,53 +628,12 @@ struct LogisticM {
   }
 };
 
-// One row's term of the Poisson log-link potential (AMH_MODEL_POISSON):
-// exp(eta) - y eta, the product rounded before the difference.  The group
-// kernel and the MFMA kernel (amh_split.hip) both call this.
-__device__ __forceinline__ float poisson_term(float eta, float y) { return amh_expf(eta) - (y * eta); }
-
+// aliases: dispatch() and the pooled launchers name the models, and the
+// kernels' symbols keep these names
 template <int G>
-struct PoissonM {
-  // z = [Intercept, b (K)]; data = [X (N x K) | y (N) | o (N) | iI2, ib2, c0]
-  // Straight VALU restatement with the shape of LogisticM: 32 partial sums
-  // whatever the group width, lane r < 32 sums rows n = r, r + 32, ..., and the
-  // lanes above 32 of a G = 64 group (the pooled kernels) hold +0.
-  static_assert(G >= 32, "the Poisson model runs at lane-group width 32 (64 in the pooled kernels)");
-  struct Ctx {
-    int64_t N;
-    const float* data;
-  };
-  static __host__ __device__ size_t lds_bytes(const ModelArgs&, int) { return 0; }
-  static __device__ void stage(float*, const ModelArgs&, int) {}
-  static __device__ __forceinline__ Ctx prepare(const ModelArgs& m, int, int) { return Ctx{m.n, m.data}; }
-  static __device__ __forceinline__ float potential(float x, int r, int d, const Ctx& c, const float*) {
-    const int64_t N = c.N;
-    const int K = d - 1;
-    const float* X = c.data;
-    const float* Y = X + N * K;
-    const float* O = Y + N;
-    const float* pr = O + N;  // iI2, ib2, c0
-    float xb[32];
-    static_for<32>([&](auto J) { xb[J] = Grp<G>::template bcast<J>(x); });
-    const float icpt = xb[0];
-    float acc = 0.0f;
-    if (r < 32) {
-      for (int64_t n = r; n < N; n += 32) {
-        float m = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 31; ++k) {
-          if (k >= K) continue;
-          m = fmaf(X[n * K + k], xb[1 + k], m);
-        }
-        acc = acc + poisson_term((icpt + m) + O[n], Y[n]);
-      }
-    }
-    const float S = Grp<G>::sum(acc);
-    const float bb = (r >= 1 && r <= K) ? x * x : 0.0f;
-    const float B = Grp<G>::sum(bb);
-    return ((S + (0.5f * B) * pr[1]) + (0.5f * (icpt * icpt)) * pr[0]) + pr[2];
-  }
-};
+using LogisticM = GlmM<G, LogisticFam>;
+template <int G>
+using PoissonM = GlmM<G, PoissonFam>;
 
 // Diamonds through sufficient statistics (AMH_MODEL_DIAMONDS_SS).  The
 // likelihood's residual sum is an exact quadratic in (Intercept, b):

@@ -75,7 +75,7 @@ struct PotParams {
   int64_t n;
   int32_t d;
   ModelArgs model;
-  const float* xpack = nullptr;  // diamonds, logistic, poisson: the design matrix in MFMA tile order (*_pack_kernel)
+  const float* xpack = nullptr;  // diamonds, logistic, poisson: the design matrix in MFMA tile order (glm_pack_kernel)
 };
 
 struct PnxParams {
@@ -375,14 +375,11 @@ hipError_t run_asss_big_pnx(const AsssPnxParams& p, hipStream_t s);
 // batched potential, then the step kernel reading U(z') (amh_split.hip)
 bool split_model(int model_id, int d);
 constexpr int kDiaMfmaKc = 24;  // diamonds on MFMA: the reference data set's Kc (amh_split.hip)
-int64_t diamonds_pack_floats(int64_t N, int64_t K);  // 0: no MFMA path for this shape
-hipError_t run_diamonds_pack(const ModelArgs& m, float* xp, hipStream_t s);
-// logistic regression on MFMA: the tile copy of X and y for any 1 <= K <= 31 (amh_split.hip)
-int64_t logistic_pack_floats(int64_t N, int64_t K);
-hipError_t run_logistic_pack(const ModelArgs& m, float* xp, hipStream_t s);
-// Poisson regression on MFMA: the tile copy of X, y and the offset, same limits (amh_split.hip)
-int64_t poisson_pack_floats(int64_t N, int64_t K);
-hipError_t run_poisson_pack(const ModelArgs& m, float* xp, hipStream_t s);
+// the MFMA potentials' tile copy of X and the per-row side vectors (diamonds: Y;
+// logistic: y; Poisson: y and the offset), for diamonds at Kc = kDiaMfmaKc and
+// the two regressions at any 1 <= K <= 31 (amh_split.hip)
+int64_t model_pack_floats(int model_id, int64_t N, int64_t K);  // 0: no MFMA path for this model or shape
+hipError_t run_model_pack(int model_id, const ModelArgs& m, float* xp, hipStream_t s);
 // the reference diamonds data (K = 25 columns): d = 26, compiled as a fixed
 // dimension on the split path
 constexpr int kDiamondsD = 26;

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64 * kDiaWaves) void diamonds_pot_lane_kernel(PotPa
 // partial sums is fixed per register, and the tiles arrive in row order, so
 // part[R] = fmaf(e, e, part[R]) keeps every residue's row order.  Xc and Y
 // are read from a per-model tile copy in A-operand / register order
-// (diamonds_pack_kernel, made when the model is bound).  A wave serves 64
+// (glm_pack_kernel below, made when the model is bound).  A wave serves 64
 // chains (two B tiles sharing each A tile); rows past N add nothing.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -244,32 +244,7 @@ struct DiaMfma {
   static constexpr int S = (KC + 1) / 2;   // MFMA k steps per tile
   static constexpr int G = (S + 3) / 4;    // 16-B A vectors per lane per tile
   static constexpr int64_t tiles(int64_t N) { return (N + 31) / 32; }
-  static constexpr int64_t floats(int64_t N) { return tiles(N) * (G * 256 + 32); }
 };
-
-template <int KC>
-__global__ __launch_bounds__(256) void diamonds_pack_kernel(const float* __restrict__ data, int64_t N,
-                                                            float* __restrict__ xp) {
-  using T = DiaMfma<KC>;
-  const int64_t m = blockIdx.x;
-  const int t = threadIdx.x;
-  const float* X = data;
-  const float* Y = data + N * KC;
-  if (t < T::G * 64) {
-    const int g = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
-    const int64_t row = 32 * m + i;
-    f32x4 v;
-    static_for<4>([&](auto E) {
-      const int k = 2 * (4 * g + E) + h;
-      v[(int)E] = (row < N && k < KC) ? X[row * KC + k] : 0.0f;
-    });
-    ((f32x4*)xp)[(m * T::G + g) * 64 + lane] = v;
-  } else if (t < T::G * 64 + 32) {
-    const int q = t - T::G * 64, h = q >> 4, R = q & 15;
-    const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;
-    xp[T::tiles(N) * T::G * 256 + 32 * m + q] = row < N ? Y[row] : 0.0f;
-  }
-}
 
 // NB B tiles (32 chains each) per wave share every A tile.  NB = 4 halves
 // the A / Y operand loads per chain and doubles the wave's independent MFMA
@@ -387,47 +362,41 @@ __global__ __launch_bounds__(256, (NB == 2 ? 2 : 1)) void diamonds_pot_mfma_kern
   });
 }
 
-int64_t diamonds_pack_floats(int64_t N, int64_t K) {
-  return (K - 1 == kDiaMfmaKc) ? DiaMfma<kDiaMfmaKc>::floats(N) : 0;
-}
-
-hipError_t run_diamonds_pack(const ModelArgs& m, float* xp, hipStream_t s) {
-  if (m.k - 1 != kDiaMfmaKc || m.n < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(diamonds_pack_kernel<kDiaMfmaKc>, dim3((unsigned)DiaMfma<kDiaMfmaKc>::tiles(m.n)), dim3(256), 0,
-                     s, m.data, m.n, xp);
-  return hipGetLastError();
-}
-
-// --------------------------------------------------- logistic on MFMA --
-// AMH_MODEL_LOGISTIC: eta = I + X b for 32 rows x 32 chains per accumulation,
-// laid out as the diamonds kernel above (A = a 32-row tile of X, B = the
-// chains' coefficients, register R of lane (i, h) = row 32 m + (R&3) +
-// 8 (R>>2) + 4 h of chain i).  K is a run-time value: the kernel is compiled
-// for GV = 1 .. 4 A vectors per lane and tile (4 GV MFMA steps, k < 8 GV) and
-// launched with the smallest that holds K; columns k >= K are zero in BOTH
-// operands (the A tile copy and the B registers), so a padded step adds
-// fmaf(0, 0, m) = m whatever m is, inf and NaN included.  The epilogue runs on
-// the accumulator registers: t = logistic_term(I + m, y), part[R] = part[R] + t
-// -- register R's row residue mod 32 is fixed and the tiles arrive in row
-// order, so part[R] is the bit spec's partial sum of that residue.  Rows at or
-// past N are left out by a select on the register's row (their t is
-// softplus(I), or inf / NaN, never 0).  The tile copy: per tile GV * 256
-// floats of X in A-operand order, then per tile 32 floats of y in register
-// order (logistic_pack_kernel, made when the model is bound).
-struct LogMfma {
+// ------------------------------------------------------- GLMs on MFMA --
+// AMH_MODEL_LOGISTIC and AMH_MODEL_POISSON (the families of amh_device.h):
+// eta = I + X b for 32 rows x 32 chains per accumulation, laid out as the
+// diamonds kernel above (A = a 32-row tile of X, B = the chains' coefficients,
+// register R of lane (i, h) = row 32 m + (R&3) + 8 (R>>2) + 4 h of chain i).
+// K is a run-time value: the kernel is compiled for GV = 1 .. 4 A vectors per
+// lane and tile (4 GV MFMA steps, k < 8 GV) and launched with the smallest
+// that holds K; columns k >= K are zero in BOTH operands (the A tile copy and
+// the B registers), so a padded step adds fmaf(0, 0, m) = m whatever m is, inf
+// and NaN included.  The epilogue runs on the accumulator registers: t =
+// Fam::term(I + m, the row's side values), part[R] = part[R] + t -- register
+// R's row residue mod 32 is fixed and the tiles arrive in row order, so
+// part[R] is the bit spec's partial sum of that residue.  Rows at or past N
+// are left out by a select on the register's row: their term is not 0
+// (logistic: softplus(I); Poisson: e^I; or inf / NaN).  The tile copy: per
+// tile GV * 256 floats of X in A-operand order, then per tile 32 * NSIDE
+// floats, each side vector's 32 in register order (glm_pack_kernel, made when
+// the model is bound).  Diamonds' copy is this one with its Kc columns and Y
+// as the one side vector: DiaMfma<24>::G = gv(24).
+struct GlmMfma {
   static constexpr int gv(int64_t K) { return (int)((K + 7) / 8); }
   static constexpr int64_t tiles(int64_t N) { return (N + 31) / 32; }
-  static constexpr int64_t floats(int64_t N, int64_t K) { return tiles(N) * (gv(K) * 256 + 32); }
+  static constexpr int64_t floats(int64_t N, int64_t K, int nside) { return tiles(N) * (gv(K) * 256 + 32 * nside); }
 };
+static_assert(DiaMfma<kDiaMfmaKc>::G == GlmMfma::gv(kDiaMfmaKc), "diamonds reads the GLM tile copy");
 
-__global__ __launch_bounds__(256) void logistic_pack_kernel(const float* __restrict__ data, int64_t N, int K,
-                                                            float* __restrict__ xp) {
-  const int GV = LogMfma::gv(K);
-  const int64_t NT = LogMfma::tiles(N);
+// data = [X (N x K) | nside vectors of N | ...]; one block per tile
+__global__ __launch_bounds__(256) void glm_pack_kernel(const float* __restrict__ data, int64_t N, int K, int nside,
+                                                       float* __restrict__ xp) {
+  const int GV = GlmMfma::gv(K);
+  const int64_t NT = GlmMfma::tiles(N);
   const int64_t m = blockIdx.x;
   const int t = threadIdx.x;
   const float* X = data;
-  const float* Y = data + N * K;
+  const float* side = data + N * K;
   if (t < GV * 64) {
     const int g = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
     const int64_t row = 32 * m + i;
@@ -438,21 +407,21 @@ __global__ __launch_bounds__(256) void logistic_pack_kernel(const float* __restr
     });
     ((f32x4*)xp)[(m * GV + g) * 64 + lane] = v;
   }
-  if (t >= 256 - 32) {
-    const int q = t - (256 - 32), h = q >> 4, R = q & 15;
+  if (t >= 256 - 32 * nside) {
+    const int q = t - (256 - 32 * nside), which = q >> 5, h = (q >> 4) & 1, R = q & 15;
     const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;
-    xp[NT * GV * 256 + 32 * m + q] = row < N ? Y[row] : 0.0f;
+    xp[NT * GV * 256 + 32 * nside * m + q] = row < N ? side[which * N + row] : 0.0f;
   }
 }
 
-constexpr int kLogNB = 2;  // B tiles (32 chains each) per wave, sharing every A tile
-template <int GV>
-__global__ __launch_bounds__(256, 2) void logistic_pot_mfma_kernel(PotParams p) {
-  constexpr int S = 4 * GV, NB = kLogNB;
+constexpr int kGlmNB = 2;  // B tiles (32 chains each) per wave, sharing every A tile
+template <class Fam, int GV>
+__global__ __launch_bounds__(256, 2) void glm_pot_mfma_kernel(PotParams p) {
+  constexpr int S = 4 * GV, NB = kGlmNB, NSIDE = Fam::NSIDE;
   const int d = p.d;
   const int K = d - 1;
   const int64_t N = p.model.n;
-  const int64_t NT = LogMfma::tiles(N);
+  const int64_t NT = GlmMfma::tiles(N);
   const int64_t n_ch = p.n;
   const int lane = lane_id();
   const int i = lane & 31, h = lane >> 5;
@@ -472,19 +441,19 @@ __global__ __launch_bounds__(256, 2) void logistic_pot_mfma_kernel(PotParams p) 
     icq[J] = zq[J][0];
   });
   const f32x4* xa = (const f32x4*)p.xpack + lane;
-  const f32x4* ya = (const f32x4*)(p.xpack + NT * GV * 256) + 4 * h;
+  const f32x4* ya = (const f32x4*)(p.xpack + NT * GV * 256) + 4 * h;  // side vector V is 8 V vectors on
   float part[NB][16];
   static_for<NB>([&](auto J) { static_for<16>([&](auto R) { part[J][R] = 0.0f; }); });
-  f32x4 a[GV], y[4];
+  f32x4 a[GV], sd[NSIDE][4];
   static_for<GV>([&](auto Q) { a[Q] = xa[64 * Q]; });
-  static_for<4>([&](auto Q) { y[Q] = ya[Q]; });
+  static_for<4>([&](auto Q) { static_for<NSIDE>([&](auto V) { sd[V][Q] = ya[8 * V + Q]; }); });
   // one tile: the MFMA steps of each B tile, then the epilogue; FULL: every
   // row exists (all tiles but the last: no per-register row test)
   auto tile = [&](int64_t m, auto FULL) {
-    f32x4 an[GV], yn[4];
+    f32x4 an[GV], sn[NSIDE][4];
     const int64_t mn = (m + 1 < NT) ? m + 1 : m;  // next tile's loads in flight during this one
     static_for<GV>([&](auto Q) { an[Q] = xa[(mn * GV + Q) * 64]; });
-    static_for<4>([&](auto Q) { yn[Q] = ya[8 * mn + Q]; });
+    static_for<4>([&](auto Q) { static_for<NSIDE>([&](auto V) { sn[V][Q] = ya[8 * NSIDE * mn + 8 * V + Q]; }); });
     f32x16 acc[NB];
     static_for<NB>([&](auto J) { acc[J] = f32x16{}; });
     static_for<S>([&](auto Q) {
@@ -494,9 +463,10 @@ __global__ __launch_bounds__(256, 2) void logistic_pot_mfma_kernel(PotParams p) 
     const int64_t nrem = N - 32 * m;  // rows of this tile that exist
     static_for<16>([&](auto R) {
       const int rr = (R & 3) + 8 * (R >> 2) + 4 * h;
-      const float yv = y[R / 4][R % 4];
+      float sv[NSIDE];
+      static_for<NSIDE>([&](auto V) { sv[V] = sd[V][R / 4][R % 4]; });
       static_for<NB>([&](auto J) {
-        const float t = logistic_term(icq[J] + acc[J][(int)R], yv);
+        const float t = Fam::term(icq[J] + acc[J][(int)R], sv);
         if constexpr (decltype(FULL)::value) {
           part[J][R] = part[J][R] + t;
         } else {
@@ -505,14 +475,14 @@ __global__ __launch_bounds__(256, 2) void logistic_pot_mfma_kernel(PotParams p) 
       });
     });
     static_for<GV>([&](auto Q) { a[Q] = an[Q]; });
-    static_for<4>([&](auto Q) { y[Q] = yn[Q]; });
+    static_for<4>([&](auto Q) { static_for<NSIDE>([&](auto V) { sd[V][Q] = sn[V][Q]; }); });
   };
 #pragma unroll 1
   for (int64_t m = 0; m + 1 < NT; ++m) tile(m, std::true_type{});
   if (NT > 0) tile(NT - 1, std::false_type{});
   // chain pair (2P, 2P + 1): lane (i, 0) finishes chain 2P, lane (i, 1) chain
   // 2P + 1; the other half's residues arrive by a 32-lane swap
-  const float* pr = p.model.data + N * K + N;  // iI2, ib2, c0
+  const float* pr = p.model.data + N * K + NSIDE * N;  // iI2, ib2, c0
   const float iI2 = pr[0], ib2 = pr[1], c0 = pr[2];
   static_for<NB / 2>([&](auto PP) {
     constexpr int P0 = 2 * PP, P1 = 2 * PP + 1;
@@ -548,216 +518,60 @@ __global__ __launch_bounds__(256, 2) void logistic_pot_mfma_kernel(PotParams p) 
   });
 }
 
-int64_t logistic_pack_floats(int64_t N, int64_t K) { return (N >= 1 && K >= 1 && K <= 31) ? LogMfma::floats(N, K) : 0; }
-
-hipError_t run_logistic_pack(const ModelArgs& m, float* xp, hipStream_t s) {
-  if (m.k < 1 || m.k > 31 || m.n < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(logistic_pack_kernel, dim3((unsigned)LogMfma::tiles(m.n)), dim3(256), 0, s, m.data, m.n, (int)m.k,
-                     xp);
-  return hipGetLastError();
-}
-
-static hipError_t run_logistic_potential(const PotParams& p, hipStream_t s) {
+template <class Fam>
+static hipError_t run_glm_potential(const PotParams& p, hipStream_t s) {
   if (p.xpack == nullptr || p.model.k != p.d - 1 || p.model.n < 1) return hipErrorInvalidValue;
-  constexpr int per_block = 4 * 32 * kLogNB;
+  constexpr int per_block = 4 * 32 * kGlmNB;
   const dim3 grid((unsigned)((p.n + per_block - 1) / per_block));
-  switch (LogMfma::gv(p.model.k)) {
+  switch (GlmMfma::gv(p.model.k)) {
     case 1:
-      hipLaunchKernelGGL(logistic_pot_mfma_kernel<1>, grid, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((glm_pot_mfma_kernel<Fam, 1>), grid, dim3(256), 0, s, p);
       break;
     case 2:
-      hipLaunchKernelGGL(logistic_pot_mfma_kernel<2>, grid, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((glm_pot_mfma_kernel<Fam, 2>), grid, dim3(256), 0, s, p);
       break;
     case 3:
-      hipLaunchKernelGGL(logistic_pot_mfma_kernel<3>, grid, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((glm_pot_mfma_kernel<Fam, 3>), grid, dim3(256), 0, s, p);
       break;
     default:
-      hipLaunchKernelGGL(logistic_pot_mfma_kernel<4>, grid, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((glm_pot_mfma_kernel<Fam, 4>), grid, dim3(256), 0, s, p);
       break;
   }
   return hipGetLastError();
 }
 
-// ---------------------------------------------------- Poisson on MFMA --
-// AMH_MODEL_POISSON: a sibling of the logistic kernel above with the same
-// geometry (A = a 32-row tile of X, B = the coefficients of 32 chains, GV =
-// ceil(K / 8) A vectors per lane and tile, columns k >= K zero in both
-// operands, register R of lane (i, h) = row 32 m + (R&3) + 8 (R>>2) + 4 h of
-// chain i).  The epilogue on the accumulator registers is eta = (I + m) + o,
-// t = poisson_term(eta, y), part[R] = part[R] + t.  Rows at or past N are left
-// out by a select on the register's row: their term is e^I, not 0.  The tile
-// copy: per tile GV * 256 floats of X in A-operand order, then per tile 64
-// floats, y and then the offset, each 32 in register order
-// (poisson_pack_kernel, made when the model is bound).
-struct PoiMfma {
-  static constexpr int gv(int64_t K) { return LogMfma::gv(K); }
-  static constexpr int64_t tiles(int64_t N) { return LogMfma::tiles(N); }
-  static constexpr int64_t floats(int64_t N, int64_t K) { return tiles(N) * (gv(K) * 256 + 64); }
-};
-
-__global__ __launch_bounds__(256) void poisson_pack_kernel(const float* __restrict__ data, int64_t N, int K,
-                                                           float* __restrict__ xp) {
-  const int GV = PoiMfma::gv(K);
-  const int64_t NT = PoiMfma::tiles(N);
-  const int64_t m = blockIdx.x;
-  const int t = threadIdx.x;
-  const float* X = data;
-  const float* YO = data + N * K;  // y (N), then o (N)
-  if (t < GV * 64) {
-    const int g = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
-    const int64_t row = 32 * m + i;
-    f32x4 v;
-    static_for<4>([&](auto E) {
-      const int k = 2 * (4 * g + E) + h;
-      v[(int)E] = (row < N && k < K) ? X[row * K + k] : 0.0f;
-    });
-    ((f32x4*)xp)[(m * GV + g) * 64 + lane] = v;
-  }
-  if (t >= 256 - 64) {
-    const int q = t - (256 - 64), which = q >> 5, h = (q >> 4) & 1, R = q & 15;
-    const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;
-    xp[NT * GV * 256 + 64 * m + q] = row < N ? YO[which * N + row] : 0.0f;
-  }
-}
-
-template <int GV>
-__global__ __launch_bounds__(256, 2) void poisson_pot_mfma_kernel(PotParams p) {
-  constexpr int S = 4 * GV, NB = kLogNB;
-  const int d = p.d;
-  const int K = d - 1;
-  const int64_t N = p.model.n;
-  const int64_t NT = PoiMfma::tiles(N);
-  const int64_t n_ch = p.n;
-  const int lane = lane_id();
-  const int i = lane & 31, h = lane >> 5;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  const int64_t cb = ((int64_t)blockIdx.x * 4 + w) * (32 * NB);
-  int64_t cq[NB];
-  const float* zq[NB];
-  float B[NB][S];
-  float icq[NB];
-  static_for<NB>([&](auto J) {
-    cq[J] = cb + 32 * J + i;
-    zq[J] = p.z + (cq[J] < n_ch ? cq[J] : n_ch - 1) * d;
-    static_for<S>([&](auto Q) {
-      const int k = 2 * Q + h;
-      B[J][Q] = k < K ? zq[J][1 + k] : 0.0f;
-    });
-    icq[J] = zq[J][0];
-  });
-  const f32x4* xa = (const f32x4*)p.xpack + lane;
-  const f32x4* ya = (const f32x4*)(p.xpack + NT * GV * 256) + 4 * h;  // y; the offset 8 vectors on
-  float part[NB][16];
-  static_for<NB>([&](auto J) { static_for<16>([&](auto R) { part[J][R] = 0.0f; }); });
-  f32x4 a[GV], y[4], o[4];
-  static_for<GV>([&](auto Q) { a[Q] = xa[64 * Q]; });
-  static_for<4>([&](auto Q) {
-    y[Q] = ya[Q];
-    o[Q] = ya[8 + Q];
-  });
-  // one tile: the MFMA steps of each B tile, then the epilogue; FULL: every
-  // row exists (all tiles but the last: no per-register row test)
-  auto tile = [&](int64_t m, auto FULL) {
-    f32x4 an[GV], yn[4], on[4];
-    const int64_t mn = (m + 1 < NT) ? m + 1 : m;  // next tile's loads in flight during this one
-    static_for<GV>([&](auto Q) { an[Q] = xa[(mn * GV + Q) * 64]; });
-    static_for<4>([&](auto Q) {
-      yn[Q] = ya[16 * mn + Q];
-      on[Q] = ya[16 * mn + 8 + Q];
-    });
-    f32x16 acc[NB];
-    static_for<NB>([&](auto J) { acc[J] = f32x16{}; });
-    static_for<S>([&](auto Q) {
-      const float av = a[Q / 4][Q % 4];
-      static_for<NB>([&](auto J) { acc[J] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B[J][Q], acc[J], 0, 0, 0); });
-    });
-    const int64_t nrem = N - 32 * m;  // rows of this tile that exist
-    static_for<16>([&](auto R) {
-      const int rr = (R & 3) + 8 * (R >> 2) + 4 * h;
-      const float yv = y[R / 4][R % 4], ov = o[R / 4][R % 4];
-      static_for<NB>([&](auto J) {
-        const float t = poisson_term((icq[J] + acc[J][(int)R]) + ov, yv);
-        if constexpr (decltype(FULL)::value) {
-          part[J][R] = part[J][R] + t;
-        } else {
-          part[J][R] = (rr < nrem) ? part[J][R] + t : part[J][R];
-        }
-      });
-    });
-    static_for<GV>([&](auto Q) { a[Q] = an[Q]; });
-    static_for<4>([&](auto Q) {
-      y[Q] = yn[Q];
-      o[Q] = on[Q];
-    });
-  };
-#pragma unroll 1
-  for (int64_t m = 0; m + 1 < NT; ++m) tile(m, std::true_type{});
-  if (NT > 0) tile(NT - 1, std::false_type{});
-  // chain pair (2P, 2P + 1): lane (i, 0) finishes chain 2P, lane (i, 1) chain
-  // 2P + 1; the other half's residues arrive by a 32-lane swap
-  const float* pr = p.model.data + N * K + 2 * N;  // iI2, ib2, c0
-  const float iI2 = pr[0], ib2 = pr[1], c0 = pr[2];
-  static_for<NB / 2>([&](auto PP) {
-    constexpr int P0 = 2 * PP, P1 = 2 * PP + 1;
-    float all[32];
-    static_for<16>([&](auto R) {
-      const float mine = h ? part[P1][R] : part[P0][R];
-      const float other = __shfl_xor(h ? part[P0][R] : part[P1][R], 32, 64);
-      const int rm = (R & 3) + 8 * (R >> 2);
-      if (h == 0) {
-        all[rm] = mine;
-        all[rm + 4] = other;
-      } else {
-        all[rm + 4] = mine;
-        all[rm] = other;
-      }
-    });
-    const float Ssum = butterfly32(all);
-    const int64_t c = h ? cq[P1] : cq[P0];
-    const float* zc = h ? zq[P1] : zq[P0];
-    float bb[32];
-    static_for<32>([&](auto R) {
-      constexpr int r = R;
-      if constexpr (r >= 1) {
-        const float br = zc[r <= K ? r : 0];
-        bb[r] = (r <= K) ? br * br : 0.0f;
-      } else {
-        bb[r] = 0.0f;
-      }
-    });
-    const float Bsum = butterfly32(bb);
-    const float icpt = zc[0];
-    if (c < n_ch) p.pe[c] = ((Ssum + (0.5f * Bsum) * ib2) + (0.5f * (icpt * icpt)) * iI2) + c0;
-  });
-}
-
-int64_t poisson_pack_floats(int64_t N, int64_t K) { return (N >= 1 && K >= 1 && K <= 31) ? PoiMfma::floats(N, K) : 0; }
-
-hipError_t run_poisson_pack(const ModelArgs& m, float* xp, hipStream_t s) {
-  if (m.k < 1 || m.k > 31 || m.n < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(poisson_pack_kernel, dim3((unsigned)PoiMfma::tiles(m.n)), dim3(256), 0, s, m.data, m.n, (int)m.k,
-                     xp);
-  return hipGetLastError();
-}
-
-static hipError_t run_poisson_potential(const PotParams& p, hipStream_t s) {
-  if (p.xpack == nullptr || p.model.k != p.d - 1 || p.model.n < 1) return hipErrorInvalidValue;
-  constexpr int per_block = 4 * 32 * kLogNB;
-  const dim3 grid((unsigned)((p.n + per_block - 1) / per_block));
-  switch (PoiMfma::gv(p.model.k)) {
-    case 1:
-      hipLaunchKernelGGL(poisson_pot_mfma_kernel<1>, grid, dim3(256), 0, s, p);
-      break;
-    case 2:
-      hipLaunchKernelGGL(poisson_pot_mfma_kernel<2>, grid, dim3(256), 0, s, p);
-      break;
-    case 3:
-      hipLaunchKernelGGL(poisson_pot_mfma_kernel<3>, grid, dim3(256), 0, s, p);
-      break;
+// ---------------------------------------------------------------- tile copy --
+// The tile copy's shape for a bound model: the columns of X (0: this model or
+// shape has no MFMA path) and the number of side vectors after it.
+static int64_t pack_cols(int model_id, int64_t N, int64_t K, int* nside) {
+  if (N < 1) return 0;
+  switch (model_id) {
+    case AMH_MODEL_DIAMONDS:  // data = [Xc (N x (K-1)) | Y (N)]
+      *nside = 1;
+      return K - 1 == kDiaMfmaKc ? K - 1 : 0;
+    case AMH_MODEL_LOGISTIC:
+      *nside = LogisticFam::NSIDE;
+      return (K >= 1 && K <= 31) ? K : 0;
+    case AMH_MODEL_POISSON:
+      *nside = PoissonFam::NSIDE;
+      return (K >= 1 && K <= 31) ? K : 0;
     default:
-      hipLaunchKernelGGL(poisson_pot_mfma_kernel<4>, grid, dim3(256), 0, s, p);
-      break;
+      return 0;
   }
+}
+
+int64_t model_pack_floats(int model_id, int64_t N, int64_t K) {
+  int nside = 0;
+  const int64_t cols = pack_cols(model_id, N, K, &nside);
+  return cols > 0 ? GlmMfma::floats(N, cols, nside) : 0;
+}
+
+hipError_t run_model_pack(int model_id, const ModelArgs& m, float* xp, hipStream_t s) {
+  int nside = 0;
+  const int64_t cols = pack_cols(model_id, m.n, m.k, &nside);
+  if (cols < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(glm_pack_kernel, dim3((unsigned)GlmMfma::tiles(m.n)), dim3(256), 0, s, m.data, m.n, (int)cols,
+                     nside, xp);
   return hipGetLastError();
 }
 
@@ -784,8 +598,8 @@ hipError_t run_propose(const StepParams& p, float* xprop, hipStream_t s) {
 
 hipError_t run_potential_lane(int model_id, const PotParams& p, hipStream_t s) {
   if (!split_model(model_id, p.d)) return hipErrorInvalidValue;
-  if (model_id == AMH_MODEL_LOGISTIC) return run_logistic_potential(p, s);
-  if (model_id == AMH_MODEL_POISSON) return run_poisson_potential(p, s);
+  if (model_id == AMH_MODEL_LOGISTIC) return run_glm_potential<LogisticFam>(p, s);
+  if (model_id == AMH_MODEL_POISSON) return run_glm_potential<PoissonFam>(p, s);
   if (p.xpack != nullptr && p.model.k - 1 == kDiaMfmaKc && p.d == kDiaMfmaKc + 2) {
     constexpr int per_block = 4 * 32 * kDiaNB;
     hipLaunchKernelGGL((diamonds_pot_mfma_kernel<kDiaMfmaKc, kDiaNB>), dim3((unsigned)((p.n + per_block - 1) / per_block)),

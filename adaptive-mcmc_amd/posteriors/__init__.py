@@ -196,33 +196,34 @@ def synthetic_diamonds(N: int = 5000, K: int = 25, seed: int = 26) -> dict:
     return {"Y": Y, "X": X}
 
 
-# ------------------------------------------------------- logistic regression --
+# ------------------------------------------------- data-carrying regressions --
 # The caller's own data set (no counterpart in the reference, whose models are
-# the three PosteriorDB scripts): include/amh.h AMH_MODEL_LOGISTIC.
-class LogisticRegression(Model):
-    """Bayesian logistic regression on the caller's data: y_n ~ Bernoulli(
-    logit^-1(Intercept + X_n b)), Intercept ~ N(0, intercept_scale), b_k ~
-    N(0, prior_scale).  It has the object shape of `diamonds` (a `Model`, used
-    as ARWMH(model=...), sites Intercept and b) but carries its data itself, so
-    `model_kwargs` stays empty and every method's `data` argument is ignored."""
+# the three PosteriorDB scripts): include/amh.h AMH_MODEL_LOGISTIC and
+# AMH_MODEL_POISSON, the GLM families of csrc/amh_device.h.
+class _GlmRegression(Model):
+    """What the data-carrying regressions share: X [N, K], the two prior
+    scales, the sites Intercept and b, and the data block [X | side vectors of
+    N | iI2, ib2, c0].  `side` lists the family's per-row vectors in the
+    device's order; `c0_extra` is the family's own constant term of U."""
 
-    def __init__(self, X: np.ndarray, y: np.ndarray, prior_scale: float, intercept_scale: float):
-        self.X, self.y = X, y  # float32, as the device reads them
+    def __init__(self, name: str, model_id: int, doc: str, X: np.ndarray, side: List[np.ndarray],
+                 prior_scale: float, intercept_scale: float, c0_extra: float = 0.0):
+        self.X, self._side = X, side  # float32, as the device reads them
         self.N, self.K = X.shape
         self.prior_scale, self.intercept_scale = float(prior_scale), float(intercept_scale)
         sI, sb = self.intercept_scale, self.prior_scale
-        # iI2, ib2, c0: float64 on the host, then rounded (as the mixture's c_k)
+        # iI2, ib2, c0: float64 on the host, then rounded once (as the mixture's c_k)
         self.consts = np.array([1.0 / (sI * sI), 1.0 / (sb * sb),
                                 math.log(sI * math.sqrt(2.0 * math.pi)) +
-                                self.K * math.log(sb * math.sqrt(2.0 * math.pi))], np.float64).astype(np.float32)
-        super().__init__("logistic_regression", _lib.AMH_MODEL_LOGISTIC, self._sites, self._pack, None,
-                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Bernoulli(logit^-1(Intercept + X b))")
+                                self.K * math.log(sb * math.sqrt(2.0 * math.pi)) + c0_extra],
+                               np.float64).astype(np.float32)
+        super().__init__(name, model_id, self._sites, self._pack, None, doc)
 
     def _sites(self, data=None):
         return [Site("Intercept", 1), Site("b", self.K)]
 
     def _pack(self, data=None):
-        return np.concatenate([self.X.reshape(-1), self.y, self.consts]), (self.N, self.K)
+        return np.concatenate([self.X.reshape(-1), *self._side, self.consts]), (self.N, self.K)
 
     def sites(self, data: dict = None) -> List[Site]:
         return self._sites()
@@ -241,10 +242,9 @@ class LogisticRegression(Model):
         return self.unravel(z)
 
 
-def logistic_regression(X, y, prior_scale: float = 2.5, intercept_scale: float = 10.0) -> LogisticRegression:
-    """Registry entry for ARWMH / ASSS / PooledARWMH(model=...) and MCMC, with
-    X [N, K] (1 <= K <= 31, no intercept column: the model has its own) and y
-    [N] in {0, 1}; the data travel with the entry (init's model_kwargs = {})."""
+def _glm_design(who: str, X, prior_scale, intercept_scale) -> np.ndarray:
+    """The checks every regression factory makes of X and the two scales, with
+    the public function's name `who` in the message; returns X as float32."""
     Xa = np.asarray(_np(X))
     if Xa.ndim != 2:
         raise ValueError(f"X must be 2-D [N, K], not {Xa.ndim}-D")
@@ -252,20 +252,43 @@ def logistic_regression(X, y, prior_scale: float = 2.5, intercept_scale: float =
     if N < 1:
         raise ValueError("X needs at least one row")
     if not 1 <= K <= 31:
-        raise ValueError(f"logistic_regression supports 1 <= K <= 31 predictors, not K = {K}")
+        raise ValueError(f"{who} supports 1 <= K <= 31 predictors, not K = {K}")
     with np.errstate(over="ignore"):  # a value past float32 becomes inf and is refused below
         Xa = np.ascontiguousarray(Xa, dtype=np.float32)
     if not np.all(np.isfinite(Xa)):
         raise ValueError("X must be finite (in float32)")
+    if not (float(prior_scale) > 0 and math.isfinite(float(prior_scale))):
+        raise ValueError("prior_scale must be positive")
+    if not (float(intercept_scale) > 0 and math.isfinite(float(intercept_scale))):
+        raise ValueError("intercept_scale must be positive")
+    return Xa
+
+
+class LogisticRegression(_GlmRegression):
+    """Bayesian logistic regression on the caller's data: y_n ~ Bernoulli(
+    logit^-1(Intercept + X_n b)), Intercept ~ N(0, intercept_scale), b_k ~
+    N(0, prior_scale).  It has the object shape of `diamonds` (a `Model`, used
+    as ARWMH(model=...), sites Intercept and b) but carries its data itself, so
+    `model_kwargs` stays empty and every method's `data` argument is ignored."""
+
+    def __init__(self, X: np.ndarray, y: np.ndarray, prior_scale: float, intercept_scale: float):
+        self.y = y
+        super().__init__("logistic_regression", _lib.AMH_MODEL_LOGISTIC,
+                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Bernoulli(logit^-1(Intercept + X b))",
+                         X, [y], prior_scale, intercept_scale)
+
+
+def logistic_regression(X, y, prior_scale: float = 2.5, intercept_scale: float = 10.0) -> LogisticRegression:
+    """Registry entry for ARWMH / ASSS / PooledARWMH(model=...) and MCMC, with
+    X [N, K] (1 <= K <= 31, no intercept column: the model has its own) and y
+    [N] in {0, 1}; the data travel with the entry (init's model_kwargs = {})."""
+    Xa = _glm_design("logistic_regression", X, prior_scale, intercept_scale)
+    N = Xa.shape[0]
     ya = np.asarray(_np(y)).reshape(-1)
     if ya.shape[0] != N:
         raise ValueError(f"y has {ya.shape[0]} entries for {N} rows of X")
     if not np.all((ya == 0) | (ya == 1)):
         raise ValueError("every y must be 0 or 1")
-    if not (float(prior_scale) > 0 and math.isfinite(float(prior_scale))):
-        raise ValueError("prior_scale must be positive")
-    if not (float(intercept_scale) > 0 and math.isfinite(float(intercept_scale))):
-        raise ValueError("intercept_scale must be positive")
     return LogisticRegression(Xa, ya.astype(np.float32), prior_scale, intercept_scale)
 
 
@@ -298,49 +321,20 @@ def synthetic_logistic(N: int = 5000, K: int = 24, seed: int = 8) -> dict:
 
 
 # -------------------------------------------------------- Poisson regression --
-# The second data-carrying model (include/amh.h AMH_MODEL_POISSON): counts with
-# a log link and an optional per-row offset.
-class PoissonRegression(Model):
+# Counts with a log link and an optional per-row offset.
+class PoissonRegression(_GlmRegression):
     """Bayesian Poisson regression on the caller's data: y_n ~ Poisson(exp(
     Intercept + X_n b + offset_n)), Intercept ~ N(0, intercept_scale), b_k ~
     N(0, prior_scale).  Shaped like `LogisticRegression`: it carries its data,
     `model_kwargs` stays empty and every method's `data` argument is ignored."""
 
     def __init__(self, X: np.ndarray, y: np.ndarray, offset: np.ndarray, prior_scale: float, intercept_scale: float):
-        self.X, self.y, self.offset = X, y, offset  # float32, as the device reads them
-        self.N, self.K = X.shape
-        self.prior_scale, self.intercept_scale = float(prior_scale), float(intercept_scale)
-        sI, sb = self.intercept_scale, self.prior_scale
-        # iI2, ib2, c0 (with sum_n lgamma(y_n + 1): U is the full -log joint):
-        # float64 on the host, then rounded once
-        lg = math.fsum(math.lgamma(float(v) + 1.0) for v in y)
-        self.consts = np.array([1.0 / (sI * sI), 1.0 / (sb * sb),
-                                math.log(sI * math.sqrt(2.0 * math.pi)) +
-                                self.K * math.log(sb * math.sqrt(2.0 * math.pi)) + lg], np.float64).astype(np.float32)
-        super().__init__("poisson_regression", _lib.AMH_MODEL_POISSON, self._sites, self._pack, None,
-                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Poisson(exp(Intercept + X b + offset))")
-
-    def _sites(self, data=None):
-        return [Site("Intercept", 1), Site("b", self.K)]
-
-    def _pack(self, data=None):
-        return np.concatenate([self.X.reshape(-1), self.y, self.offset, self.consts]), (self.N, self.K)
-
-    def sites(self, data: dict = None) -> List[Site]:
-        return self._sites()
-
-    def dim(self, data: dict = None) -> int:
-        return self.K + 1
-
-    def pack(self, data: dict = None, device="cpu") -> Tuple[torch.Tensor, Tuple[int, ...]]:
-        return super().pack(data, device)
-
-    def unravel(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
-        # b keeps its axis at K = 1 (a Site of size 1 would lose it)
-        return {"Intercept": z[..., 0], "b": z[..., 1:self.K + 1]}
-
-    def postprocess(self, z: torch.Tensor, data: dict = None) -> Dict[str, torch.Tensor]:
-        return self.unravel(z)
+        self.y, self.offset = y, offset
+        # c0 holds sum_n lgamma(y_n + 1): U is the full -log joint
+        super().__init__("poisson_regression", _lib.AMH_MODEL_POISSON,
+                         "Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~ Poisson(exp(Intercept + X b + offset))",
+                         X, [y, offset], prior_scale, intercept_scale,
+                         c0_extra=math.fsum(math.lgamma(float(v) + 1.0) for v in y))
 
 
 def poisson_regression(X, y, offset=None, prior_scale: float = 2.5,
@@ -350,18 +344,8 @@ def poisson_regression(X, y, offset=None, prior_scale: float = 2.5,
     own), counts y [N] (non-negative integers up to 2^24) and an optional
     offset [N] (log exposure); the data travel with the entry (init's
     model_kwargs = {})."""
-    Xa = np.asarray(_np(X))
-    if Xa.ndim != 2:
-        raise ValueError(f"X must be 2-D [N, K], not {Xa.ndim}-D")
-    N, K = Xa.shape
-    if N < 1:
-        raise ValueError("X needs at least one row")
-    if not 1 <= K <= 31:
-        raise ValueError(f"poisson_regression supports 1 <= K <= 31 predictors, not K = {K}")
-    with np.errstate(over="ignore"):  # a value past float32 becomes inf and is refused below
-        Xa = np.ascontiguousarray(Xa, dtype=np.float32)
-    if not np.all(np.isfinite(Xa)):
-        raise ValueError("X must be finite (in float32)")
+    Xa = _glm_design("poisson_regression", X, prior_scale, intercept_scale)
+    N = Xa.shape[0]
     ya = np.asarray(_np(y)).reshape(-1).astype(np.float64)
     if ya.shape[0] != N:
         raise ValueError(f"y has {ya.shape[0]} entries for {N} rows of X")
@@ -377,10 +361,6 @@ def poisson_regression(X, y, offset=None, prior_scale: float = 2.5,
             oa = np.ascontiguousarray(oa, dtype=np.float32)
         if not np.all(np.isfinite(oa)):
             raise ValueError("offset must be finite (in float32)")
-    if not (float(prior_scale) > 0 and math.isfinite(float(prior_scale))):
-        raise ValueError("prior_scale must be positive")
-    if not (float(intercept_scale) > 0 and math.isfinite(float(intercept_scale))):
-        raise ValueError("intercept_scale must be positive")
     return PoissonRegression(Xa, ya.astype(np.float32), oa, prior_scale, intercept_scale)
 
 

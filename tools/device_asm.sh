@@ -1,7 +1,8 @@
 #!/bin/bash
 # device assembly of every csrc/*.hip, for proving that a refactor changed no
 # kernel: tools/device_asm.sh OUTDIR [extra hipcc flags] -> OUTDIR/<name>.s
-# Run it on two checkouts and `diff -r` the two OUTDIRs. Lines with the
+# Run it on two checkouts and `diff -r` the two OUTDIRs, or compare them
+# function by function with tools/asm_diff.py. Lines with the
 # compiler's per-translation-unit __hip_cuid_<hash> symbol are dropped.
 set -e -o pipefail
 OUTDIR=$(mkdir -p "$1" && cd "$1" && pwd); shift
