@@ -31,7 +31,8 @@
 
 #define ORC_DMAX 64
 
-enum { ORC_GAUSSIAN = 1, ORC_EIGHT_SCHOOLS = 2, ORC_KIDIQ = 3, ORC_DIAMONDS = 4, ORC_DIAMONDS_SS = 5, ORC_MIXTURE = 6 };
+enum { ORC_GAUSSIAN = 1, ORC_EIGHT_SCHOOLS = 2, ORC_KIDIQ = 3, ORC_DIAMONDS = 4, ORC_DIAMONDS_SS = 5, ORC_MIXTURE = 6,
+       ORC_LOGISTIC = 8, ORC_POISSON = 9 }; /* = AMH_MODEL_*; id 7 has no mirror */
 
 typedef struct {
   int32_t model_id;
@@ -53,9 +54,11 @@ int orc_group_width(int d) {
 }
 
 /* Group width of the per-chain kernels for a model (amh_device.h dispatch):
- * eight schools runs at G = 16 and diamonds at G = 32 for every d they take. */
+ * eight schools runs at G = 16, diamonds and the GLM models at G = 32 for every
+ * d they take. */
 static int orc_gw(const orc_cfg* cfg) {
   if (cfg->model_id == ORC_DIAMONDS || cfg->model_id == ORC_DIAMONDS_SS) return 32;
+  if (cfg->model_id == ORC_LOGISTIC || cfg->model_id == ORC_POISSON) return 32;
   if (cfg->model_id == ORC_EIGHT_SCHOOLS) return 16;
   return orc_group_width(cfg->d);
 }
@@ -308,6 +311,38 @@ static float pot_mixture(const orc_cfg* cfg, const float* x, int G) {
   return -group_sum(v, G);
 }
 
+/* Generalised linear models (amh_device.h GlmM; DESIGN.md section 4 items
+ * 5b / 5c).  z = [Intercept, b (K)], K = d - 1 = k_data; data = [X (N x K,
+ * row-major) | y (N) | o (N, Poisson only) | iI2, ib2, c0].  32 partial sums
+ * whatever G is: part[n mod 32] takes row n in row order, and the lanes
+ * 32 .. G - 1 of the pooled kernels' G = 64 group hold +0. */
+static float logistic_term(float eta, float y) {
+  return (fmaxf(eta, 0.0f) + amh_log1pf(amh_expf(-fabsf(eta)))) - y * eta;
+}
+
+static float poisson_term(float eta, float y) { return amh_expf(eta) - (y * eta); }
+
+static float pot_glm(const orc_cfg* cfg, const float* x, int G, int family) {
+  const int64_t N = cfg->n_data;
+  const int K = cfg->d - 1;
+  const float* X = cfg->data;
+  const float* y = X + N * K;
+  const float* o = y + N; /* Poisson only */
+  const float* pr = y + (family == ORC_POISSON ? 2 : 1) * N; /* iI2, ib2, c0 */
+  const float icpt = x[0];
+  float part[ORC_DMAX] = {0.0f}, bb[ORC_DMAX] = {0.0f};
+  for (int64_t n = 0; n < N; ++n) {
+    float m = 0.0f;
+    for (int k = 0; k < K; ++k) m = fmaf(X[n * K + k], x[1 + k], m);
+    const float t = (family == ORC_POISSON) ? poisson_term((icpt + m) + o[n], y[n]) : logistic_term(icpt + m, y[n]);
+    part[n & 31] = part[n & 31] + t;
+  }
+  const float S = group_sum(part, G);
+  for (int r = 0; r < G; ++r) bb[r] = (r >= 1 && r <= K) ? x[r] * x[r] : 0.0f;
+  const float B = group_sum(bb, G);
+  return ((S + (0.5f * B) * pr[1]) + (0.5f * (icpt * icpt)) * pr[0]) + pr[2];
+}
+
 static float pot_gaussian_big(const orc_cfg* cfg, const float* x);
 
 float orc_potential1(const orc_cfg* cfg, const float* x) {
@@ -320,6 +355,8 @@ float orc_potential1(const orc_cfg* cfg, const float* x) {
     case ORC_DIAMONDS: return pot_diamonds(cfg, x, G);
     case ORC_DIAMONDS_SS: return pot_diamonds_ss(cfg, x, G);
     case ORC_MIXTURE: return pot_mixture(cfg, x, G);
+    case ORC_LOGISTIC: return pot_glm(cfg, x, G, ORC_LOGISTIC);
+    case ORC_POISSON: return pot_glm(cfg, x, G, ORC_POISSON);
     default: return NAN;
   }
 }
@@ -563,7 +600,8 @@ void orc_step(const orc_cfg* cfg, int64_t C, int32_t n_steps, int32_t* i_, float
     chain_t* s = (chain_t*)malloc(sizeof(chain_t));
     /* the split transition (data-heavy models, amh_split.hip) is one launch
      * per step: the state goes through HBM (L = U diag(dl)) between steps */
-    const int split = cfg->model_id == ORC_DIAMONDS && d >= 3 && d <= 32;
+    const int glm = cfg->model_id == ORC_LOGISTIC || cfg->model_id == ORC_POISSON; /* amh_split.hip split_model */
+    const int split = (cfg->model_id == ORC_DIAMONDS && d >= 3 && d <= 32) || (glm && d >= 2 && d <= 32);
     chain_load(cfg, s, c, i_, z, pe, macc, mu, L, lam, asc);
     int nacc = 0;
     for (int32_t t = 0; t < n_steps; ++t) {
@@ -701,6 +739,8 @@ static float orc_potential_g(const orc_cfg* cfg, const float* x, int G) {
     case ORC_DIAMONDS: return pot_diamonds(cfg, x, G);
     case ORC_DIAMONDS_SS: return pot_diamonds_ss(cfg, x, G);
     case ORC_MIXTURE: return pot_mixture(cfg, x, G);
+    case ORC_LOGISTIC: return pot_glm(cfg, x, G, ORC_LOGISTIC);
+    case ORC_POISSON: return pot_glm(cfg, x, G, ORC_POISSON);
     default: return NAN;
   }
 }

@@ -211,6 +211,24 @@ def mixture_potential(z, weights, locs, scales):
     return -float(np.sum(np.log(np.exp(lp - mx).sum(axis=1)) + mx[:, 0]))
 
 
+def logistic_potential(z, X, y, prior_scale=2.5, intercept_scale=10.0):
+    """z = [Intercept, b (K)]; Intercept ~ N(0, s_I), b ~ N(0, s_b), y ~
+    Bernoulli(logit^-1(Intercept + X b)) (posteriors.logistic_regression)."""
+    icpt, b = z[0], np.asarray(z[1:])
+    eta = icpt + np.asarray(X) @ b
+    ll = np.asarray(y) * eta - np.logaddexp(0.0, eta)
+    return -(normal_lp(icpt, 0.0, intercept_scale) + np.sum(normal_lp(b, 0.0, prior_scale)) + np.sum(ll))
+
+
+def poisson_potential(z, X, y, offset, prior_scale=2.5, intercept_scale=10.0):
+    """z = [Intercept, b (K)]; the same priors, y ~ Poisson(exp(Intercept +
+    X b + offset)) with its lgamma(y + 1) term (posteriors.poisson_regression)."""
+    icpt, b = z[0], np.asarray(z[1:])
+    eta = icpt + np.asarray(X) @ b + np.asarray(offset)
+    ll = np.asarray(y) * eta - np.exp(eta) - gammaln(np.asarray(y) + 1.0)
+    return -(normal_lp(icpt, 0.0, intercept_scale) + np.sum(normal_lp(b, 0.0, prior_scale)) + np.sum(ll))
+
+
 def gaussian_potential(z, m, P, c0):
     diff = np.asarray(z) - m
     return 0.5 * diff @ (P @ diff) + c0

@@ -19,6 +19,9 @@
  * is the warmup reset from hostile values (gamma = 1, sqrt(1 - gamma) L = 0).
  * Two more d = 8 runs, ARWMH and ASSS, start every other chain from a point
  * scaled by 10^k, k in [-3, 20] (wild_starts).
+ * The GLM models (ids 8 and 9: logistic at d = 8, Poisson with offsets at
+ * d = 32, N = 77 rows, |X| < 1/4) run the hostile scenario with both samplers
+ * and the wild starts with ARWMH.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -90,15 +93,42 @@ static void hostile_adapt(state_t* s, int64_t C, int d, int step_size) {
   }
 }
 
-static int run(int d, int asss, int wild) {
+enum { GAUSSIAN = 1, LOGISTIC = 8, POISSON = 9 };
+#define GLM_N 77
+
+/* [X (N x K) | y (N) | o (N, Poisson) | iI2, ib2, c0]: |X| < 1/4, y in {0, 1}
+ * (logistic) or {0 .. 7} (Poisson), o in (-1, 1); priors N(0, 10), N(0, 2.5) */
+static float* glm_data(int model, int d) {
+  const int K = d - 1, side = model == POISSON ? 2 : 1;
+  float* data = calloc((size_t)GLM_N * (size_t)(K + side) + 3, sizeof(float));
+  uint32_t seed = 777u + (uint32_t)d;
+  for (int k = 0; k < GLM_N * K; ++k) data[k] = unif(&seed) * 0.5f - 0.25f;
+  float* y = data + GLM_N * K;
+  for (int n = 0; n < GLM_N; ++n) y[n] = (float)(lcg(&seed) >> (model == POISSON ? 29 : 31));
+  if (model == POISSON)
+    for (int n = 0; n < GLM_N; ++n) y[GLM_N + n] = unif(&seed) * 2.0f - 1.0f;
+  float* pr = y + side * GLM_N;
+  pr[0] = 0.01f;
+  pr[1] = 0.16f;
+  pr[2] = 3.2215f + (float)K * 1.8352f;
+  return data;
+}
+
+static int run(int model, int d, int asss, int wild) {
   const int64_t C = 160;
-  float* data = calloc((size_t)d + (size_t)d * d + 1, sizeof(float));
-  float* Pm = data + d;
-  for (int r = 0; r < d; ++r) {
-    Pm[r * d + r] = 2.0f + 0.01f * (float)r;
-    if (r + 1 < d) Pm[r * d + r + 1] = Pm[(r + 1) * d + r] = -0.5f;
+  float* data;
+  if (model == GAUSSIAN) {
+    data = calloc((size_t)d + (size_t)d * d + 1, sizeof(float));
+    float* Pm = data + d;
+    for (int r = 0; r < d; ++r) {
+      Pm[r * d + r] = 2.0f + 0.01f * (float)r;
+      if (r + 1 < d) Pm[r * d + r + 1] = Pm[(r + 1) * d + r] = -0.5f;
+    }
+  } else {
+    data = glm_data(model, d);
   }
-  orc_cfg cfg = {1 /* ORC_GAUSSIAN */, d, 8 /* HOSTILE_WARMUP */, 2.0f / 3.0f, 0.234f, 1e-6f, data, 0, 0};
+  orc_cfg cfg = {model, d, 8 /* HOSTILE_WARMUP */, 2.0f / 3.0f, 0.234f, 1e-6f, data,
+                 model == GAUSSIAN ? 0 : GLM_N, model == GAUSSIAN ? 0 : d - 1};
   state_t s = alloc_state(C, d);
   float* z0 = calloc(C * d, sizeof(float));
   uint32_t seed = 12345u + (uint32_t)d;
@@ -131,7 +161,7 @@ static int run(int d, int asss, int wild) {
     nonfinite += bad;
     moved += memcmp(s.z + c * d, z0 + c * d, sizeof(float) * (size_t)d) != 0;
   }
-  printf("d=%d %s%s: %lld of %lld chains with a non-finite factor, %lld moved\n", d, asss ? "asss" : "arwmh",
+  printf("model %d d=%d %s%s: %lld of %lld chains with a non-finite factor, %lld moved\n", model, d, asss ? "asss" : "arwmh",
          wild ? " wild" : "", (long long)nonfinite, (long long)C, (long long)moved);
   const int ok = s.i[0] == 21;
   free(acc); free(z0); free_state(&s); free(data);
@@ -141,10 +171,14 @@ static int run(int d, int asss, int wild) {
 int main(void) {
   int rc = 0;
   for (int asss = 0; asss < 2; ++asss) {
-    rc |= run(8, asss, 0);
-    rc |= run(100, asss, 0);
+    rc |= run(GAUSSIAN, 8, asss, 0);
+    rc |= run(GAUSSIAN, 100, asss, 0);
+    rc |= run(LOGISTIC, 8, asss, 0);
+    rc |= run(POISSON, 32, asss, 0);
   }
-  rc |= run(8, 0, 1);
-  rc |= run(8, 1, 1);
+  rc |= run(GAUSSIAN, 8, 0, 1);
+  rc |= run(GAUSSIAN, 8, 1, 1);
+  rc |= run(LOGISTIC, 8, 0, 1);
+  rc |= run(POISSON, 32, 0, 1);
   return rc;
 }

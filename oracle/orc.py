@@ -22,6 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("AMH_ORACLE_LIB") or os.path.join(_HERE, "build", "libamh_oracle.so")
 
 GAUSSIAN, EIGHT_SCHOOLS, KIDIQ, DIAMONDS, DIAMONDS_SS, MIXTURE = 1, 2, 3, 4, 5, 6
+LOGISTIC, POISSON = 8, 9  # = AMH_MODEL_*; id 7 has no mirror
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64

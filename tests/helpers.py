@@ -35,7 +35,39 @@ def make_case(kind: str, d: int = None):
         mx = P.notebook_mixture() if (d or 1) == 1 else P.mixture([0.5, 0.5], [-1.0, 1.0], [0.1, 0.1], dim=d)
         data, ip = mx.pack("cpu")
         return dict(potential_fn=mx), {}, orc.Model(orc.MIXTURE, mx.dim, data.numpy(), n_data=ip[0])
+    if kind in ("logistic", "poisson"):
+        return glm_case(kind, d or 8, GLM_N)
     raise ValueError(kind)
+
+
+# rows of make_case's GLM data: ten 32-row tiles, the last one ragged
+GLM_N = 300
+# column scale of that data.  Every |X_nk| stays below 1, so a single
+# coefficient of 3e38 (helpers.edge_points) leaves every eta finite: the row
+# terms stay finite or overflow to +inf, b'b overflows, and U is +inf, not NaN.
+# Poisson's smaller scale keeps |eta| below amh_expf's range at a coefficient
+# of +-200, which the finite share of test_edge_points_reach needs.
+GLM_X_SCALE = {"logistic": 0.25, "poisson": 0.0625}
+
+
+def glm_case(kind, d, N, seed=None):
+    """make_case for the GLM models at any N: posteriors.synthetic_logistic /
+    synthetic_poisson (with offsets) at K = d - 1, the columns scaled by
+    GLM_X_SCALE and clipped to [-1, 1]; the oracle reads the entry's own packed
+    float32 data."""
+    import orc
+    import posteriors as P
+    K = d - 1
+    seed = 100 * d + N % 100 if seed is None else seed
+    mk = P.synthetic_logistic(N, K, seed) if kind == "logistic" else P.synthetic_poisson(N, K, seed)
+    X = np.clip(mk["X"] * np.float32(GLM_X_SCALE[kind]), -1.0, 1.0).astype(np.float32)
+    if kind == "logistic":
+        e = P.logistic_regression(X, mk["y"])
+    else:
+        e = P.poisson_regression(X, mk["y"], mk["offset"])
+    arr, (N_, K_) = e.pack_fn(None)
+    return dict(model=e), {}, orc.Model(orc.LOGISTIC if kind == "logistic" else orc.POISSON, K + 1, arr,
+                                        n_data=N_, k_data=K_)
 
 
 def state_to_orc(state):
@@ -206,12 +238,17 @@ def hostile_adapt(state, step_size=True, factors=FACTOR_CYCLE, step_sizes=STEP_S
 # the model matrix of the edge tests (tests/test_edges.py, tests/test_gpu_edges.py)
 EDGE_MATRIX = [("gaussian", 1), ("gaussian", 5), ("gaussian", 33), ("gaussian", 64), ("gaussian", 72),
                ("gaussian", 100), ("gaussian", 128), ("gaussian", 256), ("eight_schools", None), ("kidiq", None),
-               ("diamonds", None), ("diamonds_n77", None), ("diamonds_ss", None), ("mixture", 1), ("mixture", 3)]
+               ("diamonds", None), ("diamonds_n77", None), ("diamonds_ss", None), ("mixture", 1), ("mixture", 3),
+               ("logistic", 8), ("logistic", 32), ("logistic_n77", 8), ("logistic_n77", 32),
+               ("poisson", 9), ("poisson", 32), ("poisson_n77", 9), ("poisson_n77", 32)]
 
 
 def make_edge_case(kind, d=None):
     """make_case plus "diamonds_n77": the literal diamonds model off the
-    compile-time fast path (N = 77, K = 10; the generic split transition)."""
+    compile-time fast path (N = 77, K = 10; the generic split transition), and
+    "logistic_n77" / "poisson_n77": the GLM models off the 32-row tile (N = 77)."""
+    if kind in ("logistic_n77", "poisson_n77"):
+        return glm_case(kind[:-4], d or 8, 77)
     if kind == "diamonds_n77":
         import orc
         import posteriors as P

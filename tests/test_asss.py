@@ -11,12 +11,13 @@ import numpy as np
 import pytest
 
 import asss_np as lit
-from helpers import make_case
+from helpers import make_case, make_edge_case
 from test_oracle import lit_potential, unpack
 
 
 def _step_compare(kind, pre, orc, C=48, d=None):
-    _, _, om = make_case(kind, d)
+    _, _, om = make_edge_case(kind, d)
+    kind = kind.replace("_n77", "")
     from kernels_amd import PRNGKey
     st = orc.init(om, PRNGKey(7), C)
     if pre:
@@ -52,7 +53,10 @@ def _step_compare(kind, pre, orc, C=48, d=None):
 @pytest.mark.parametrize("kind,d", [("gaussian", 12), ("gaussian", 64), ("eight_schools", None), ("kidiq", None),
                                     ("diamonds", None), ("mixture", 1), ("mixture", 3),
                                     # large d (asss_step_big1: streamed factor, potential along the circle)
-                                    ("gaussian", 96), ("gaussian", 128), ("gaussian", 100), ("gaussian", 97)])
+                                    ("gaussian", 96), ("gaussian", 128), ("gaussian", 100), ("gaussian", 97),
+                                    # the GLM models at K = 7 / 31, N = 77
+                                    ("logistic_n77", 8), ("logistic_n77", 32),
+                                    ("poisson_n77", 8), ("poisson_n77", 32)])
 @pytest.mark.parametrize("pre", [0, 1, 23])
 def test_oracle_step_matches_literal(kind, d, pre, orc):
     _step_compare(kind, pre, orc, C=24 if kind in ("diamonds", "gaussian") else 48, d=d)

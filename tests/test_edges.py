@@ -79,7 +79,25 @@ MEASURED_POTENTIAL_REL = {
     ("gaussian", 72): 3.7e-7, ("gaussian", 100): 7.9e-7, ("gaussian", 128): 5.5e-7, ("gaussian", 256): 1.1e-6,
     ("eight_schools", None): 1.7e-7, ("kidiq", None): 3.2e-7, ("diamonds", None): 2.7e-7,
     ("diamonds_n77", None): 2.1e-7, ("diamonds_ss", None): 2.8e-7, ("mixture", 1): 6.2e-8, ("mixture", 3): 1.2e-7,
+    ("logistic", 8): 1.6e-7, ("logistic", 32): 1.6e-7, ("logistic_n77", 8): 1.9e-7, ("logistic_n77", 32): 1.4e-7,
+    # Poisson: e^eta carries eta's absolute error as a relative one, and the anchor rows reach |eta| ~ 60
+    # (a coefficient of +-200 on columns of scale 1/16): (K + 2) |eta| 2^-24 is 4e-5 at K = 8
+    ("poisson", 9): 3.5e-6, ("poisson", 32): 7.9e-6, ("poisson_n77", 9): 2.0e-6, ("poisson_n77", 32): 7.8e-6,
 }
+
+
+def _poisson_eta_out_of_range(om, z):
+    """Rows of z at which some eta_n = I + X_n b + o_n, evaluated in float64 on
+    the float32 data, lies past log(FLT_MAX) = 88.72, where amh_expf returns
+    +inf (then U is +inf, or inf - inf = NaN once y_n eta_n overflows too), or
+    at which |y_n eta_n| itself is past float32's range (eta_n very negative)."""
+    N, K = om.n_data, om.k_data
+    raw = np.asarray(om.data, np.float64)
+    X, y, o = raw[:N * K].reshape(N, K), raw[N * K:N * K + N], raw[N * K + N:N * K + 2 * N]
+    z = z.astype(np.float64)
+    with np.errstate(all="ignore"):
+        eta = z[:, :1] + z[:, 1:] @ X.T + o
+        return ~(eta.max(1) <= 88.72) | ~(np.abs(y * eta).max(1) <= 3.4e38)
 
 
 @pytest.mark.parametrize("kind,d", EDGE_MATRIX)
@@ -96,7 +114,11 @@ def test_potential_anchor(kind, d, orc):
     log-scale coordinate exceeds 88 in magnitude, or the float64 value exceeds
     1e37.  (Before amh_log1p_sqf this failed for kidiq and diamonds at
     log sigma = 87: the half-Cauchy / Student-t prior squared sigma / s in
-    float32, +inf from sigma ~ 4e19 on, where U is about N log sigma.)"""
+    float32, +inf from sigma ~ 4e19 on, where U is about N log sigma.)
+    Poisson exponentiates every row's eta, not a coordinate: there the oracle
+    may also be non-finite where a float64 eta_n is past amh_expf's range
+    (_poisson_eta_out_of_range).  On these rows the clause adds nothing to the
+    1e37 rule (e^88.72 alone is 3.4e38), which the test asserts."""
     _, _, om = make_edge_case(kind, d)
     lc = log_scale_coords(_base(kind), om.d)
     _, z = edge_points(om.d, 11, lc)
@@ -111,6 +133,10 @@ def test_potential_anchor(kind, d, orc):
     with np.errstate(invalid="ignore"):
         use = np.isfinite(ul) & (np.abs(ul) < 1e30) & ~logbig & infin
         allowed = ~infin | logbig | ~(np.abs(ul) <= 1e37)
+    if _base(kind) == "poisson":
+        eta_out = _poisson_eta_out_of_range(om, z) & infin
+        assert not (eta_out & ~allowed).any()
+        allowed |= eta_out
     assert use.sum() >= 0.5 * len(z)
     fin = np.isfinite(pe)
     finding = ~fin & ~allowed
@@ -301,7 +327,8 @@ def test_asss_step_anchor(orc):
 # -------------------------------------------- host undefined-behaviour run ----
 def test_oracle_edge_steps_under_sanitizers():
     """oracle/edge_ubsan.c (own main, no Python): 12 ARWMH and 12 ASSS oracle
-    steps of a d = 8 and a d = 100 Gaussian from hostile_adapt states, built
+    steps of a d = 8 and a d = 100 Gaussian, a d = 8 logistic and a d = 32
+    Poisson regression (N = 77) from hostile_adapt states, built
     with -fsanitize=address,undefined,float-cast-overflow and no recovery; a
     report (an out-of-range float -> int cast, say) would mark a point where
     host and device may legitimately differ.  Exit status 0 expected."""

@@ -55,7 +55,10 @@ def _init(kind, C, orc, seed=0, d=None, num_warmup=0):
                                       ("gaussian", 96, 130), ("gaussian", 128, 100), ("gaussian", 256, 70),
                                       # any 64 < d <= 256 (round 6): ragged tile / dword DMA / odd d
                                       ("gaussian", 72, 90), ("gaussian", 100, 77), ("gaussian", 97, 65),
-                                      ("gaussian", 160, 50), ("gaussian", 150, 40)])
+                                      ("gaussian", 160, 50), ("gaussian", 150, 40),
+                                      # the GLM models (GlmM in the chain's lane group)
+                                      ("logistic", 8, 300), ("logistic", 32, 130), ("poisson", 8, 300),
+                                      ("poisson", 32, 130)])
 def test_asss_single_steps_bitexact(kind, d, C, gpu, orc):
     """ASSS.sample (one launch per step, out of place) vs oracle, 25 steps."""
     k, st, om, ost = _init(kind, C, orc, d=d, num_warmup=8)
@@ -68,7 +71,9 @@ def test_asss_single_steps_bitexact(kind, d, C, gpu, orc):
 
 
 @pytest.mark.parametrize("kind,d,C", [("gaussian", 64, 1000), ("eight_schools", None, 700), ("diamonds", None, 40),
-                                      ("gaussian", 128, 60), ("gaussian", 256, 33)])
+                                      ("gaussian", 128, 60), ("gaussian", 256, 33),
+                                      ("logistic", 8, 130), ("logistic", 32, 70), ("poisson", 8, 130),
+                                      ("poisson", 32, 70)])
 def test_asss_fused_and_collect_bitexact(kind, d, C, gpu, orc):
     """ASSS.run (n steps per launch, z / pe collected with thinning) and the
     in-place ASSS.sample_ vs the oracle's launch-for-launch mirror."""
@@ -98,6 +103,23 @@ def test_asss_sample_pnx_bitexact(gpu, orc):
     ref = orc.asss_sample_pnx(om, PRNGKey(9), x.cpu().numpy(), loc.cpu().numpy(), scale.cpu().numpy(), 4, 37)
     assert out.shape == (5, 37, om.d)
     np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("kind", ["logistic", "poisson"])
+@pytest.mark.parametrize("d", [8, 32])
+def test_asss_sample_pnx_glm_bitexact(kind, d, gpu, orc):
+    """The frozen slice kernel with the GLM models against orc_asss_sample_pnx."""
+    from kernels_amd import PRNGKey
+    k, st, om, ost = _init(kind, 16, orc, d=d)
+    k.sample_(st, 20)
+    a = st.adapt_state
+    loc, scale = a.loc[3].clone(), a.scale[3].clone()
+    x = st.z[:4].clone()
+    out = k.sample_Pnx(PRNGKey(9), x, (loc, scale), n=4, n_samples=33)
+    ref = orc.asss_sample_pnx(om, PRNGKey(9), x.cpu().numpy(), loc.cpu().numpy(), scale.cpu().numpy(), 4, 33)
+    assert out.shape == (4, 33, d)
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+    assert np.any(ref != x.cpu().numpy()[:, None, :])
 
 
 @pytest.mark.parametrize("d", [128, 256, 100])

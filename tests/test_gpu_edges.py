@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 
 C = 160
 ASSS_MATRIX = [("gaussian", 1), ("gaussian", 5), ("gaussian", 64), ("gaussian", 100), ("gaussian", 256),
-               ("eight_schools", None), ("kidiq", None), ("diamonds", None), ("mixture", 3)]
+               ("eight_schools", None), ("kidiq", None), ("diamonds", None), ("mixture", 3),
+               ("logistic", 8), ("logistic", 32), ("poisson", 9), ("poisson", 32)]
 
 
 def _start(cls, kind, d, orc, start, num_warmup, seed=0):

@@ -26,7 +26,8 @@ def _init(kind, C, gpu, orc, seed=0, d=None, num_warmup=0):
     return k, st, om, ost
 
 
-@pytest.mark.parametrize("kind", ["gaussian", "eight_schools", "kidiq", "diamonds", "diamonds_ss", "mixture"])
+@pytest.mark.parametrize("kind", ["gaussian", "eight_schools", "kidiq", "diamonds", "diamonds_ss", "mixture",
+                                  "logistic", "poisson"])
 def test_init_bitexact(kind, gpu, orc):
     k, st, om, ost = _init(kind, 333, gpu, orc)
     assert_state_bitequal(st, ost, f"{kind} init")
@@ -36,7 +37,8 @@ def test_init_bitexact(kind, gpu, orc):
                                     ("eight_schools", None), ("kidiq", None), ("diamonds", None), ("diamonds_ss", None),
                                     ("gaussian", 96), ("gaussian", 256), ("gaussian", 72), ("gaussian", 100),
                                     ("gaussian", 97), ("mixture", 1), ("mixture", 3),
-                                    ("mixture", 16)])
+                                    ("mixture", 16), ("logistic", 8), ("logistic", 32), ("poisson", 9),
+                                    ("poisson", 32)])
 def test_potential_bitexact(kind, d, gpu, orc):
     k, st, om, ost = _init(kind, 8, gpu, orc, d=d)
     z = np.random.default_rng(1).normal(size=(1000, om.d)).astype(np.float32)
@@ -48,7 +50,10 @@ def test_potential_bitexact(kind, d, gpu, orc):
 @pytest.mark.parametrize("kind,d,C", [("gaussian", 64, 1000), ("gaussian", 7, 517), ("gaussian", 32, 300),
                                       ("eight_schools", None, 400), ("kidiq", None, 257),
                                       ("diamonds", None, 66), ("diamonds_ss", None, 333), ("mixture", 1, 1000),
-                                      ("mixture", 5, 300), ("gaussian", 1, 1000), ("gaussian", 2, 333)])
+                                      ("mixture", 5, 300), ("gaussian", 1, 1000), ("gaussian", 2, 333),
+                                      # the GLM models: propose / MFMA potential / step (the split path)
+                                      ("logistic", 8, 517), ("logistic", 32, 300), ("poisson", 8, 517),
+                                      ("poisson", 32, 300)])
 def test_single_steps_bitexact(kind, d, C, gpu, orc):
     """ARWMH.sample (one launch per step) vs oracle step(n_steps=1), 40 steps."""
     k, st, om, ost = _init(kind, C, gpu, orc, d=d, num_warmup=10)
@@ -62,7 +67,8 @@ def test_single_steps_bitexact(kind, d, C, gpu, orc):
 
 
 @pytest.mark.parametrize("kind,d,C", [("gaussian", 64, 2000), ("eight_schools", None, 1000), ("gaussian", 1, 777),
-                                      ("diamonds", None, 130), ("diamonds_ss", None, 1000)])
+                                      ("diamonds", None, 130), ("diamonds_ss", None, 1000),
+                                      ("logistic", 17, 130), ("poisson", 17, 130)])
 def test_fused_steps_bitexact(kind, d, C, gpu, orc):
     """ARWMH.run (n steps in one launch, z collected) vs oracle step(n_steps)."""
     k, st, om, ost = _init(kind, C, gpu, orc, d=d)
@@ -295,7 +301,7 @@ def test_diamonds_suffstat_generic_k(gpu, orc):
     np.testing.assert_array_equal(pe.view(np.uint32), orc.potential(om, z).view(np.uint32))
 
 
-@pytest.mark.parametrize("kind,d,C", [("gaussian", 128, 65), ("diamonds", None, 66)])
+@pytest.mark.parametrize("kind,d,C", [("gaussian", 128, 65), ("diamonds", None, 66), ("logistic", 17, 66)])
 def test_big_dim_chained_proposal_invalidation(kind, d, C, gpu, orc):
     """d > 64 and the literal diamonds split path: sample() reuses the proposal
     the previous step pass formed only for the unchanged state it returned: an
@@ -358,7 +364,7 @@ def _head(st, n):
     return type(st)(*[type(x)(*[y[:n] for y in x]) if isinstance(x, tuple) else x[:n] for x in st])
 
 
-@pytest.mark.parametrize("kind,d,C", [("gaussian", 96, 65), ("diamonds", None, 66)])
+@pytest.mark.parametrize("kind,d,C", [("gaussian", 96, 65), ("diamonds", None, 66), ("poisson", 17, 66)])
 def test_library_ready_guard(kind, d, C, gpu, orc):
     """The library's own guard on AMH_STEP_PROPOSAL_READY: it honours the flag
     only for the very buffers, and the chain count, of the call that kept the

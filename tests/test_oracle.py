@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import arwmh_np as lit
-from helpers import make_case
+from helpers import make_case, make_edge_case
 
 # fp32 potentials of magnitude |U| carry ~|U| * 2^-23 absolute error into alpha,
 # hence into lambda and mean_accept_prob.
@@ -42,6 +42,16 @@ def lit_potential(kind, om):
         return lambda z: lit.diamonds_potential(z, data[:N * Kc].reshape(N, Kc), data[N * Kc:])
     if kind == "mixture":  # the notebook's weights / locs / scales (helpers.make_case)
         return lambda z: lit.mixture_potential(z, [0.5, 0.5], [-1.0, 1.0], [0.1, 0.1])
+    if kind in ("logistic", "poisson"):  # the product's own float64 potentials on the bytes the oracle reads
+        import types
+        import posteriors as P
+        N, K = om.n_data, om.k_data
+        raw = np.asarray(om.data, np.float32)
+        e = types.SimpleNamespace(X=raw[:N * K].reshape(N, K), y=raw[N * K:N * K + N], consts=raw[-3:])
+        if kind == "logistic":
+            return lambda z: float(P.logistic_potential_f64(np.asarray(z, np.float64), e))
+        e.offset = raw[N * K + N:N * K + 2 * N]
+        return lambda z: float(P.poisson_potential_f64(np.asarray(z, np.float64), e))
     raise ValueError(kind)
 
 
@@ -93,14 +103,18 @@ def test_nan_potential_rejects():
                                       ("gaussian", 256), ("mixture", 1), ("mixture", 3),
                                       # large d off the 32-multiples: a ragged MFMA tile,
                                       # dword-DMA column blocks, an odd d
-                                      ("gaussian", 72), ("gaussian", 100), ("gaussian", 97)])
+                                      ("gaussian", 72), ("gaussian", 100), ("gaussian", 97),
+                                      # the GLM models at K = 7 / 31, N = 77 (model 4's tolerances)
+                                      ("logistic_n77", 8), ("logistic_n77", 32),
+                                      ("poisson_n77", 8), ("poisson_n77", 32)])
 @pytest.mark.parametrize("pre_steps", [0, 1, 37])
 def test_oracle_step_matches_literal(kind, dim, pre_steps, orc):
     """One teacher-forced transition (identical noise) of the C oracle against
     the literal float64 restatement; d = 128 / 256 exercise the large-d bit
     spec (wave-per-chain passes, MFMA-order potential)."""
     from kernels_amd import PRNGKey
-    _, _, om = make_case(kind, dim)
+    _, _, om = make_edge_case(kind, dim)
+    kind = kind.replace("_n77", "")
     d, C, W = om.d, (48 if om.d <= 64 else 12), 20
     st = orc.init(om, PRNGKey(3), C)
     if pre_steps:
@@ -135,6 +149,26 @@ def test_oracle_step_matches_literal(kind, dim, pre_steps, orc):
         assert abs(st.as_change[c] - new.as_change) <= 1e-3 * abs(new.as_change) + 1e-5, ctx
         assert st.i[c] == new.i
     assert checked >= C - 2
+
+
+@pytest.mark.parametrize("kind,d", [("logistic", 8), ("logistic_n77", 32), ("poisson", 9), ("poisson_n77", 32)])
+def test_glm_potentials_agree_in_float64(kind, d, orc):
+    """The two float64 statements of the GLM potentials -- posteriors.*_f64 (the
+    device's own grouping and its float32 constants iI2, ib2, c0) and
+    arwmh_np's (the model written from its densities, lgamma included) --
+    agree to the rounding of the three float32 constants: |dU| <= 2^-23 times
+    (|c0| + the two prior terms), on uniform(-2, 2) points."""
+    _, _, om = make_edge_case(kind, d)
+    base = kind.replace("_n77", "")
+    U = lit_potential(base, om)
+    N, K = om.n_data, om.k_data
+    raw = np.asarray(om.data, np.float64)
+    X, y, o = raw[:N * K].reshape(N, K), raw[N * K:N * K + N], raw[N * K + N:N * K + 2 * N]
+    iI2, ib2, c0 = raw[-3:]
+    for z in np.random.default_rng(d).uniform(-2, 2, size=(20, om.d)):
+        ref = lit.logistic_potential(z, X, y) if base == "logistic" else lit.poisson_potential(z, X, y, o)
+        bound = 2.0 ** -23 * (abs(c0) + 0.5 * z[1:] @ z[1:] * ib2 + 0.5 * z[0] ** 2 * iI2) + 1e-12 * abs(ref)
+        assert abs(U(z) - ref) <= bound, (U(z), ref, bound)
 
 
 # ------------------------------------------------------------ known answers --

@@ -28,14 +28,40 @@ def test_layout(orc):
     assert orc.pooled_cpw(65536) == 16 and orc.pooled_cpw(10 ** 7) == 16
 
 
-@pytest.mark.parametrize("name,model_id,d", [("eight_schools", 2, 10), ("gaussian64", 1, 64)])
+def _glm_golden(kind, d, steps=100):
+    """What a golden file holds, for one chain of a GLM case (helpers.glm_case,
+    N = 77), made here by the producer of the golden files (tests/golden/
+    make_golden.py `run`: oracle/arwmh_np.py fed the build's Philox noise)
+    around the float64 potential of tests/test_oracle.py."""
+    import importlib.util
+    import arwmh_np as lit
+    from helpers import glm_case
+    from test_oracle import lit_potential
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(G, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    _, _, om = glm_case(kind, d, 77)
+    keys = lit.chain_keys(np.array([0, 0], np.uint32), 0, 1)
+    z0 = np.random.default_rng(d).uniform(-2, 2, size=(1, d)).astype(np.float32)
+    f = mg.run(lit_potential(kind, om), d, z0, keys, steps, [1, 2, 5, 10, 20, 50, 100])
+    f.update(init_z=z0, chain_keys=keys)
+    return om, f
+
+
+@pytest.mark.parametrize("name,model_id,d", [("eight_schools", 2, 10), ("gaussian64", 1, 64),
+                                             ("logistic", 8, 8), ("poisson", 9, 9)])
 def test_one_chain_is_the_reference_recurrence(name, model_id, d, orc):
     """N = 1: mu' = mu + gamma delta, Sigma' = (1-gamma) Sigma + gamma delta delta^T
     refactorised -- the reference's rank-one update (arwmh.py:188-191), so the
-    pooled chain follows the golden trajectory of chain 0."""
+    pooled chain follows the golden trajectory of chain 0 (the GLM models: the
+    same producer's trajectory, made in the test)."""
     from test_golden import tol
-    f = np.load(os.path.join(G, name + ".npz"))
-    om = orc.Model(model_id, d, f["model_data"])
+    if name in ("logistic", "poisson"):
+        om, f = _glm_golden(name, d)
+        assert om.model_id == model_id
+    else:
+        f = np.load(os.path.join(G, name + ".npz"))
+        om = orc.Model(model_id, d, f["model_data"])
     z = f["init_z"][:1].copy()
     pe = orc.potential(om, z)
     keys = f["chain_keys"][:1].copy()
@@ -183,7 +209,8 @@ def _shared_copy(sh):
 
 
 @pytest.mark.parametrize("kind,d,C,K", [("gaussian", 12, 37, 4), ("eight_schools", None, 70, 3),
-                                        ("gaussian", 128, 40, 3), ("gaussian", 64, 300, 5)])
+                                        ("gaussian", 128, 40, 3), ("gaussian", 64, 300, 5),
+                                        ("logistic", 8, 70, 3), ("poisson", 32, 70, 4)])
 def test_block_is_k_frozen_steps(kind, d, C, K, orc):
     """A block of K transitions (orc_pooled_stats_k) is K single pooled steps
     with the shared state frozen: per-chain z / pe bit for bit, the sums equal
