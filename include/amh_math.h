@@ -9,11 +9,19 @@
  * transcendental is called, because those differ between host and device.
  * Both sides are compiled with -ffp-contract=off so nothing else fuses.
  *
- * The functions are pinned independently of this file by
- * tests/test_rng_math.py (the host compile: numpy/scipy float64 references and
- * Random123 KAT vectors for Philox4x32-10) and, for the device compile, by
- * tests/test_gpu_eval.py::test_normals_bitexact (amh_normals against the host
- * compile, bit for bit: Philox, amh_logf, sqrtf and both erfinv polynomials).
+ * The functions are pinned independently of this file, compile by compile:
+ *   - the gcc host compile (the C oracle) by tests/test_rng_math.py: Random123
+ *     KAT vectors for Philox4x32-10 and numpy/scipy float64 references for every
+ *     function below, subnormal arguments and results included;
+ *   - the device compile by tests/test_gpu_math.py: every function below, and
+ *     the row terms of amh_device.h, as an elementwise probe kernel
+ *     (csrc/amh_probe.hip) against the gcc compile, bit for bit, on the input
+ *     sets of tests/math_cases.py (every exponent, the subnormal band, +-0,
+ *     +-inf, NaN, +-64 ulp around every branch constant and rint tie; all 2^23
+ *     normals), and through Philox by tests/test_gpu_eval.py::test_normals_bitexact;
+ *   - hipcc's host compile, which fills the gamma table of amh_create, by
+ *     tests/test_rng_math.py::test_three_compiles_agree against the gcc compile.
+ * NaN payloads are not part of the spec; a function's stated domain is.
  *
  * Reference anchors (what the noise stands in for):
  *   arwmh.py:162  rng_key, key_proposal, key_accept = random.split(rng_key, 3)
@@ -316,7 +324,10 @@ __device__ __forceinline__ float amh_erfinv_tail(float w0) {
 /* Cephes-style single precision sin and cos of one argument (the slice
  * angle of ASSS, asss.py:69, :95: |theta| < 2 pi).  theta = k pi/2 + r with
  * k = rint(theta 2/pi) and a three-part Cody-Waite reduction (fmaf), then the
- * sinf / cosf minimax polynomials on |r| <= pi/4 and the quadrant swap. */
+ * sinf / cosf minimax polynomials on |r| <= pi/4 and the quadrant swap.
+ * Domain: finite |x| <= 2^30.  Beyond it (int)kf leaves the range of int,
+ * which C leaves undefined, so the compiles may differ there (and the
+ * reduction has long lost its accuracy); the bit-for-bit pin stops at 2^30. */
 AMH_HD void amh_sincosf(float x, float* s_out, float* c_out) {
   const float kf = rintf(x * 0.636619772367581343f);
   const int k = (int)kf;

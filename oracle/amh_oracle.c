@@ -695,6 +695,26 @@ void orc_log1pf(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n
 void orc_erfinvf(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_erfinvf(x[i]); }
 void orc_normal_bits(const uint32_t* b, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_normal_from_bits(b[i]); }
 void orc_lr_gamma(const int32_t* nn, float a, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_lr_gamma(nn[i], a); }
+void orc_sincosf(const float* x, float* s, float* c, int64_t n) { for (int64_t i = 0; i < n; ++i) amh_sincosf(x[i], s + i, c + i); }
+void orc_log1p_sqf(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_log1p_sqf(x[i]); }
+void orc_log1p_sq3f(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_log1p_sq3f(x[i]); }
+void orc_rsqrt_nr(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_rsqrt_nr(x[i]); }
+void orc_unif01(const uint32_t* b, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_unif01_from_bits(b[i]); }
+void orc_pivot_ok(const float* x, int32_t* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_pivot_ok(x[i]); }
+void orc_isfinite(const float* x, int32_t* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_isfinite(x[i]); }
+void orc_isnan(const float* x, int32_t* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_isnan(x[i]); }
+void orc_log_d(const double* x, double* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_log_d(x[i]); }
+void orc_exp_d(const double* x, double* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = amh_exp_d(x[i]); }
+/* one row's term of the GLM potentials and the Student-t(3) log prior, as the potentials above call them */
+void orc_logistic_term(const float* eta, const float* y, float* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = logistic_term(eta[i], y[i]);
+}
+void orc_poisson_term(const float* eta, const float* y, float* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = poisson_term(eta[i], y[i]);
+}
+void orc_lp_student3(const float* x, float loc, float scale, float c, float* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = lp_student3(x[i], loc, scale, c);
+}
 int orc_num_threads(void) {
 #ifdef _OPENMP
   extern int omp_get_max_threads(void);

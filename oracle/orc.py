@@ -69,10 +69,12 @@ def lib():
         L.orc_step.argtypes = [_P, _I64, _I32] + [_P] * 11
         L.orc_sample_pnx.argtypes = [_P, _P, _P, _I64, _I64, _P, _P, _F, _I32, _P]
         L.orc_philox.argtypes = [_P, _P, _P, _I64]
-        for name in ("orc_logf", "orc_expf", "orc_log1pf", "orc_erfinvf"):
-            getattr(L, name).argtypes = [_P, _P, _I64]
-        L.orc_normal_bits.argtypes = [_P, _P, _I64]
         L.orc_lr_gamma.argtypes = [_P, _F, _P, _I64]
+        for name in _EW_1IN:
+            getattr(L, "orc_" + name).argtypes = [_P, _P, _I64]
+        for name in ("orc_sincosf", "orc_logistic_term", "orc_poisson_term"):
+            getattr(L, name).argtypes = [_P, _P, _P, _I64]
+        L.orc_lp_student3.argtypes = [_P, _F, _F, _F, _P, _I64]
         L.orc_num_threads.restype = ctypes.c_int
         L.orc_asss_step.argtypes = [_P, _I64, _I32] + [_P] * 9
         L.orc_asss_step.restype = None
@@ -99,11 +101,45 @@ def _c(a, dtype):
 
 
 # ------------------------------------------------------------ elementwise --
-def elementwise(name: str, x: np.ndarray) -> np.ndarray:
+# one input, one output: name -> (input dtype, output dtype)
+_EW_1IN = {
+    "logf": (np.float32, np.float32), "expf": (np.float32, np.float32), "log1pf": (np.float32, np.float32),
+    "erfinvf": (np.float32, np.float32), "log1p_sqf": (np.float32, np.float32),
+    "log1p_sq3f": (np.float32, np.float32), "rsqrt_nr": (np.float32, np.float32),
+    "unif01": (np.uint32, np.float32), "normal_bits": (np.uint32, np.float32),
+    "pivot_ok": (np.float32, np.int32), "isfinite": (np.float32, np.int32), "isnan": (np.float32, np.int32),
+    "log_d": (np.float64, np.float64), "exp_d": (np.float64, np.float64),
+}
+
+
+def elementwise(name: str, x: np.ndarray, *args):
+    """The host compile of one function of include/amh_math.h (or one row term
+    of the potentials) over an array.  One-input functions: see _EW_1IN.
+    "sincosf" returns (sin, cos); "logistic_term" / "poisson_term" take
+    (eta, y); "lp_student3" takes (x, loc, scale, c)."""
+    if name in _EW_1IN:
+        tin, tout = _EW_1IN[name]
+        x = _c(x, tin)
+        y = np.empty(x.shape, tout)
+        getattr(lib(), "orc_" + name)(_ptr(x), _ptr(y), x.size)
+        return y
     x = _c(x, np.float32)
-    y = np.empty_like(x)
-    getattr(lib(), "orc_" + name)(_ptr(x), _ptr(y), x.size)
-    return y
+    if name == "sincosf":
+        s, c = np.empty_like(x), np.empty_like(x)
+        lib().orc_sincosf(_ptr(x), _ptr(s), _ptr(c), x.size)
+        return s, c
+    out = np.empty_like(x)
+    if name in ("logistic_term", "poisson_term"):
+        (y,) = args
+        y = _c(y, np.float32)
+        assert y.shape == x.shape
+        getattr(lib(), "orc_" + name)(_ptr(x), _ptr(y), _ptr(out), x.size)
+        return out
+    if name == "lp_student3":
+        loc, scale, c = args
+        lib().orc_lp_student3(_ptr(x), loc, scale, c, _ptr(out), x.size)
+        return out
+    raise KeyError(name)
 
 
 def philox(ctr: np.ndarray, key: np.ndarray) -> np.ndarray:
