@@ -1,7 +1,8 @@
 // amh_asss.h -- one ASSS transition (python/kernels/asss.py:197-251) of a
 // lane group's chain, shared by the ASSS kernels (amh_asss.hip), the d = 64
-// persistent step kernel's ASSS instantiation (amh_step64.hip) and, piece by
-// piece, the kernels around a caller's potential (amh_asss_ext.hip).  Bit spec:
+// persistent step kernel's ASSS instantiation (amh_step64.hip), pooled ASSS
+// (amh_pooled_asss.hip) and, piece by piece, the kernels around a caller's
+// potential (amh_asss_ext.hip, amh_pooled_asss_ext.hip).  Bit spec:
 // oracle/amh_oracle.c orc_asss_step.
 #pragma once
 #include "amh_device.h"
@@ -20,10 +21,13 @@ enum : int {
 static_assert(kNumScalars <= kAsssExtScalars, "record too small");
 
 // The pieces of one transition (asss.py:197-251), each written once: the fused
-// transition below runs them back to back with the model's potential inside;
-// the external-potential kernels (amh_asss_ext.hip) run the same pieces cut at
-// every potential evaluation, with the caller's U in between.  A group of G
-// lanes owns the chain, lane r holds row r; `act` = r < d.
+// transitions (asss_transition below, pooled_asss_transition of
+// amh_pooled_asss.hip) run them back to back, with the model's potential
+// inside asss_slice_walk; asss_big_chain (amh_big.hip) runs the scalar ones in
+// a wave-uniform loop of its own; the external-potential kernels
+// (amh_asss_ext.hip) run the same pieces cut at every potential evaluation,
+// with the caller's U in between.  A group of G lanes owns the chain, lane r
+// holds row r; `act` = r < d.
 
 // ---- the chain's factor from its packed lower triangle L (column j holds
 // rows j .. d-1): lane r gets dl = L_rr and row r in unit-lower form, U[j] =
@@ -183,15 +187,97 @@ __device__ __forceinline__ float asss_narrow(float th, float thmin, float thmax,
   return thmin_n + (thmax_n - thmin_n) * amh_unif01_from_bits(ok.v[0]);
 }
 
-// the transition's outcome: theta = 0 (the point x0, its U0) when the tangent
-// was degenerate or the shrinkage hit its cap (asss.py:94), else the accepted
-// candidate; NaN -> +inf (asss.py:234)
+// whether the transition left theta = 0: not when the tangent was degenerate
+// or the shrinkage hit its cap after `iter` rounds (asss.py:94)
+__device__ __forceinline__ bool asss_moved(bool degen, int32_t iter) { return !(degen || iter >= kAsssMaxIter); }
+
+// the transition's outcome: theta = 0 (the point x0, its U0) when it did not
+// move, else the accepted candidate; NaN -> +inf (asss.py:234)
 __device__ __forceinline__ void asss_outcome(bool degen, int32_t iter, float x0, float xt, float U0, float ux,
                                              float& xnew, float& pen) {
-  const bool capped = degen || iter >= kAsssMaxIter;
+  const bool capped = !asss_moved(degen, iter);
   xnew = capped ? x0 : xt;
   pen = capped ? U0 : ux;
   if (amh_isnan(pen)) pen = INFINITY;
+}
+
+// The initial scalar slots kZd .. kKey1 of a chain's record around a caller's
+// potential (one lane writes them): the bracket of the first candidate th0,
+// whose om is `om`, no round run yet.
+__device__ __forceinline__ void asss_ext_record_init(float* sc, float zd, float vd, float th0, float ut, float om0,
+                                                     float om, bool degen, int32_t it, uint32_t k0, uint32_t k1) {
+  int32_t* si = (int32_t*)sc;
+  sc[kZd] = zd;
+  sc[kVd] = vd;
+  sc[kTh] = th0;
+  sc[kThmin] = th0 - 6.28318548f;
+  sc[kThmax] = th0;
+  si[kIter] = 0;
+  sc[kUt] = ut;
+  sc[kOm0] = om0;
+  sc[kOm] = om;
+  si[kDegen] = degen ? 1 : 0;
+  si[kCont] = 1;
+  sc[kTpe] = 0.0f;
+  sc[kU0] = 0.0f;
+  sc[kUx] = 0.0f;
+  si[kIt] = it;
+  si[kKey0] = (int32_t)k0;
+  si[kKey1] = (int32_t)k1;
+}
+
+// ---- the slice walk (asss.py:216-226, 59-96) on the circle (Sz, Sv, zd, vd,
+// mu) with the potential `Uof`: x -> U (lane r's coordinate in, the group's U
+// out): the level at theta = 0, the first candidate th0, the shrinkage -- every
+// lane of the wave stays in the loop until no group continues, a group that
+// has stopped keeps its point -- and the outcome (xnew, pen).  Returns the
+// shrink count.  (The inputs come by reference: copied by value, the pooled
+// kernel's DiamondsSS instance, at the 128-VGPR cap, spills 16 bytes more.)
+template <class UF>
+__device__ __forceinline__ int32_t asss_slice_walk(const float& Sz, const float& Sv, const float& zd, const float& vd,
+                                                   const float& mu, const bool& act, const bool& degen,
+                                                   const float& ut, const float& th0, const float& fd,
+                                                   const float& eps, const int32_t& it, const uint32_t& k0,
+                                                   const uint32_t& k1, UF&& Uof, float& xnew, float& pen) {
+  // ---- slice level at z
+  float om0;
+  const float x0 = asss_x_at(Sz, Sv, zd, vd, mu, act, 1.0f, 0.0f, om0);
+  const float U0 = Uof(x0);
+  const float tpe = asss_level(U0, fd, om0, ut);
+
+  // ---- shrinkage (asss.py:59-96)
+  float th = th0, thmin = th0 - 6.28318548f, thmax = th0;
+  int32_t iter = 0;
+  float xt, ux;
+  bool cont;
+  {
+    float s, c, om;
+    amh_sincosf(th, &s, &c);
+    xt = asss_x_at(Sz, Sv, zd, vd, mu, act, c, s, om);
+    ux = Uof(xt);
+    const float pt = asss_slice_pt(ux, fd, om);
+    cont = !degen && ((pt > tpe) || (om < eps));
+  }
+  while (__ballot(cont) != 0ull) {
+    float thmin_n, thmax_n;
+    const float th_n = asss_narrow(th, thmin, thmax, iter, it, k0, k1, thmin_n, thmax_n);
+    float s, c, om;
+    amh_sincosf(th_n, &s, &c);
+    const float xn = asss_x_at(Sz, Sv, zd, vd, mu, act, c, s, om);
+    const float un = Uof(xn);
+    const float pt = asss_slice_pt(un, fd, om);
+    if (cont) {
+      thmin = thmin_n;
+      thmax = thmax_n;
+      th = th_n;
+      xt = xn;
+      ux = un;
+      iter += 1;
+      cont = (iter < kAsssMaxIter) && ((pt > tpe) || (om < eps));
+    }
+  }
+  asss_outcome(degen, iter, x0, xt, U0, ux, xnew, pen);
+  return iter;
 }
 
 // ---- adaptation (asss.py:237-251) with the new point xnew: as ARWMH
@@ -281,45 +367,10 @@ __device__ __forceinline__ void asss_transition(const StepParams& p, float (&U)[
   const bool degen = asss_tangent<G>(act, zr, zd, v, vd);
   asss_circle<DMAX>(U, dl, sd, p.eps, zr, v, d, Sz, Sv);
 
-  // ---- slice level at z
-  float om0;
-  const float x0 = asss_x_at(Sz, Sv, zd, vd, mu, act, 1.0f, 0.0f, om0);
-  const float U0 = M<G>::potential(x0, r, d, mctx, lds);
-  const float tpe = asss_level(U0, fd, om0, ut);
-
-  // ---- shrinkage (asss.py:59-96)
-  float th = th0, thmin = th0 - 6.28318548f, thmax = th0;
-  int32_t iter = 0;
-  float xt, ux;
-  bool cont;
-  {
-    float s, c, om;
-    amh_sincosf(th, &s, &c);
-    xt = asss_x_at(Sz, Sv, zd, vd, mu, act, c, s, om);
-    ux = M<G>::potential(xt, r, d, mctx, lds);
-    const float pt = asss_slice_pt(ux, fd, om);
-    cont = !degen && ((pt > tpe) || (om < p.eps));
-  }
-  while (__ballot(cont) != 0ull) {
-    float thmin_n, thmax_n;
-    const float th_n = asss_narrow(th, thmin, thmax, iter, it, k0, k1, thmin_n, thmax_n);
-    float s, c, om;
-    amh_sincosf(th_n, &s, &c);
-    const float xn = asss_x_at(Sz, Sv, zd, vd, mu, act, c, s, om);
-    const float un = M<G>::potential(xn, r, d, mctx, lds);
-    const float pt = asss_slice_pt(un, fd, om);
-    if (cont) {
-      thmin = thmin_n;
-      thmax = thmax_n;
-      th = th_n;
-      xt = xn;
-      ux = un;
-      iter += 1;
-      cont = (iter < kAsssMaxIter) && ((pt > tpe) || (om < p.eps));
-    }
-  }
   float xnew, pen;
-  asss_outcome(degen, iter, x0, xt, U0, ux, xnew, pen);
+  asss_slice_walk(Sz, Sv, zd, vd, mu, act, degen, ut, th0, fd, p.eps, it, k0, k1,
+                  [&](float xx) __attribute__((always_inline)) { return M<G>::potential(xx, r, d, mctx, lds); }, xnew,
+                  pen);
   if constexpr (ADAPT) asss_adapt<DMAX>(p, U, dl, mu, asc, updated, it, xnew, d, rr, act);
   x = xnew;
   pe = pen;

@@ -104,27 +104,7 @@ __global__ __launch_bounds__(kBlock) void asss_ext_begin_kernel(AsssExtParams q)
         w[d + r] = Sv;
         w[2 * d + r] = mu;
       }
-      if (r == 0) {
-        float* sc = w + 3 * d;
-        int32_t* si = (int32_t*)sc;
-        sc[kZd] = zd;
-        sc[kVd] = vd;
-        sc[kTh] = th0;
-        sc[kThmin] = th0 - 6.28318548f;
-        sc[kThmax] = th0;
-        si[kIter] = 0;
-        sc[kUt] = ut;
-        sc[kOm0] = om0;
-        sc[kOm] = om;
-        si[kDegen] = degen ? 1 : 0;
-        si[kCont] = 1;
-        sc[kTpe] = 0.0f;
-        sc[kU0] = 0.0f;
-        sc[kUx] = 0.0f;
-        si[kIt] = it;
-        si[kKey0] = (int32_t)k0;
-        si[kKey1] = (int32_t)k1;
-      }
+      if (r == 0) asss_ext_record_init(w + 3 * d, zd, vd, th0, ut, om0, om, degen, it, k0, k1);
     }
   }
 }

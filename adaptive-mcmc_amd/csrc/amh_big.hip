@@ -27,6 +27,7 @@
 // count is one read and one write); the passes stream it with coalesced
 // column accesses and keep nothing but O(d) per chain on chip.
 // Bit spec: oracle/amh_oracle.c, "large dimensions".
+#include "amh_asss.h"
 #include "amh_device.h"
 
 namespace amh {
@@ -34,11 +35,6 @@ namespace amh {
 namespace {
 
 constexpr int kNSMAX = 4;  // row slots per lane: d <= 64 * NS, NS = 2 (d <= 128) or 4
-constexpr int kAsssBigMaxIter = 50;  // asss.py:59 max_iterations
-
-__device__ __forceinline__ float rdl(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
 
 // gamma_n (scalar cache table, as the step kernel)
 __device__ __forceinline__ float big_gamma(const BigParams& p, int32_t n) {
@@ -230,8 +226,8 @@ __global__ __launch_bounds__(256) void big_propose_kernel(BigParams p) {
     for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&v)[NS]) {
       constexpr int kb = KB;
       const int jl = j - 64 * kb;
-      const float etaj = rdl(eta[kb], jl);
-      const float invj = rdl(inv[kb], jl);
+      const float etaj = rdlane(eta[kb], jl);
+      const float invj = rdlane(inv[kb], jl);
       // row j completes its proposal and both solves at its own column
       if (lane == jl) {
         acc[kb] = fmaf(1.0f, etaj, acc[kb]);
@@ -239,8 +235,8 @@ __global__ __launch_bounds__(256) void big_propose_kernel(BigParams p) {
         wa[kb] = (zp[kb] - mu[kb]) - sa[kb];
         wr[kb] = (zz[kb] - mu[kb]) - sr[kb];
       }
-      const float waj = rdl(wa[kb], jl);
-      const float wrj = rdl(wr[kb], jl);
+      const float waj = rdlane(wa[kb], jl);
+      const float wrj = rdlane(wr[kb], jl);
       static_for<NS>([&](auto K) {
         if constexpr (K >= kb) {
           const int r = 64 * K + lane;
@@ -332,7 +328,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       const bool act = r < d;
       const float e = Grp<64>::excl_scan(t[K], lane);
       const float bs = (K == 0) ? e : e + carry;
-      const float tot = rdl(e + t[K], 63);
+      const float tot = rdlane(e + t[K], 63);
       carry = (K == 0) ? tot : carry + tot;
       const float b = 1.0f + bs;
       const float g2 = (b * Dg[K]) + gw2[K];
@@ -364,16 +360,16 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       if constexpr (NEXT) {
         constexpr int kb = KB;
         const int jl = j - 64 * kb;
-        const float etaj = rdl(neta[kb], jl);
-        const float invj = rdl(ninv[kb], jl);
+        const float etaj = rdlane(neta[kb], jl);
+        const float invj = rdlane(ninv[kb], jl);
         if (lane == jl) {
           nacc[kb] = fmaf(1.0f, etaj, nacc[kb]);
           nzp[kb] = zn[kb] + fmaf(e1, nacc[kb], p.eps * nxi[kb]);
           nwa[kb] = (nzp[kb] - mun[kb]) - nsa[kb];
           nwr[kb] = (zn[kb] - mun[kb]) - nsr[kb];
         }
-        const float waj = rdl(nwa[kb], jl);
-        const float wrj = rdl(nwr[kb], jl);
+        const float waj = rdlane(nwa[kb], jl);
+        const float wrj = rdlane(nwr[kb], jl);
         static_for<NS>([&](auto K) {
           if constexpr (K >= kb) {
             const int r = 64 * K + lane;
@@ -397,8 +393,8 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       for_columns<RAG, NS>(Lin, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&v)[NS]) {
         constexpr int kb = KB;
         const int jl = j - 64 * kb;
-        const float wsj = rdl(ws[kb], jl), cj = rdl(cc[kb], jl), acj = rdl(ac[kb], jl);
-        const float bcj = rdl(bc[kb], jl), invj = rdl(inv[kb], jl), qj = rdl(qq[kb], jl);
+        const float wsj = rdlane(ws[kb], jl), cj = rdlane(cc[kb], jl), acj = rdlane(ac[kb], jl);
+        const float bcj = rdlane(bc[kb], jl), invj = rdlane(inv[kb], jl), qj = rdlane(qq[kb], jl);
         float* ocol = Lout + col_off(d, j) - j;
         if (lane == jl) {
           const float tt = fmaf(1.0f, acj, bcj * 0.0f);
@@ -431,7 +427,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       for_columns<RAG, NS>(Lin, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&v)[NS]) {
         constexpr int kb = KB;
         const int jl = j - 64 * kb;
-        const float acj = rdl(ac[kb], jl), invj = rdl(inv[kb], jl);
+        const float acj = rdlane(ac[kb], jl), invj = rdlane(inv[kb], jl);
         float* ocol = Lout + col_off(d, j) - j;
         if (lane == jl) {
           const float t0 = 1.0f * acj;
@@ -576,7 +572,7 @@ __global__ __launch_bounds__(256) void gauss_pot_mfma_kernel(PotParams p) {
       static_for<2>([&](auto T) {
         float ps = 0.0f;
         static_for<16>([&](auto R) {
-          const int row = 32 * tile + (R & 3) + 8 * (R >> 2) + 4 * h;
+          const int row = mfma_row(R, h, 32 * tile);
           ps = ps + Dt[row * kPotLd + 32 * T + i] * acc[I][T][(int)R];
         });
         const float other = __shfl_xor(ps, 32, 64);
@@ -652,14 +648,14 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
   for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
     constexpr int kb = KB;
     const int jl = j - 64 * kb;
-    const float yl = rdl(b[kb] * invD[kb], jl);
-    const float g = yl * rdl(e[kb], jl);
-    const float hvj = rdl(hv[kb], jl);
-    const float invj = rdl(inv[kb], jl);
+    const float yl = rdlane(b[kb] * invD[kb], jl);
+    const float g = yl * rdlane(e[kb], jl);
+    const float hvj = rdlane(hv[kb], jl);
+    const float invj = rdlane(inv[kb], jl);
     float wyj = 0.0f, wvj = 0.0f;
     if constexpr (ADAPT) {
-      wyj = yl - rdl(ty[kb], jl);
-      wvj = rdl(v[kb] - tv[kb], jl);
+      wyj = yl - rdlane(ty[kb], jl);
+      wvj = rdlane(v[kb] - tv[kb], jl);
     }
     if (lane == jl) {
       y[kb] = yl;
@@ -728,7 +724,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
         });
         static_for<8>([&](auto T) {
           const int kl = k2 + T;
-          const float sa = rdl(Sz[kb], kl), sb = rdl(Sv[kb], kl), sg = rdl(gm[kb], kl);
+          const float sa = rdlane(Sz[kb], kl), sb = rdlane(Sv[kb], kl), sg = rdlane(gm[kb], kl);
           static_for<NS>([&](auto K) {
             Pa[K] = fmaf(pr[T][K], sa, Pa[K]);
             Pb[K] = fmaf(pr[T][K], sb, Pb[K]);
@@ -755,7 +751,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
   // ---- slice level and shrinkage (asss.py:216-239, 59-96)
   float x0[NS], xt[NS], om0;
   const float U0 = eval(1.0f, 0.0f, x0, om0);
-  const float tpe = (U0 + fd * amh_logf(om0)) - amh_logf(ut);
+  const float tpe = asss_level(U0, fd, om0, ut);
   float th = th0, thmin = th0 - 6.28318548f, thmax = th0;
   int32_t iter = 0;
   float ux, cst, snt, omt;  // the angle of xt
@@ -767,27 +763,22 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
     cst = cs;
     snt = sn;
     omt = om;
-    float pt = ux + fd * amh_logf(om);
-    if (amh_isnan(pt)) pt = INFINITY;
+    const float pt = asss_slice_pt(ux, fd, om);
     cont = !degen && ((pt > tpe) || (om < eps));
   }
   while (cont) {  // wave-uniform: one chain per wave
-    if (th < 0.0f) thmin = th;
-    if (th >= 0.0f) thmax = th;
-    const amh_u32x4 o = amh_philox4x32_10((uint32_t)iter, (uint32_t)it, 1u, AMH_TAG_ASSS, k0, k1);
-    th = thmin + (thmax - thmin) * amh_unif01_from_bits(o.v[0]);
+    th = asss_narrow(th, thmin, thmax, iter, it, k0, k1, thmin, thmax);
     float sn, cs, om;
     amh_sincosf(th, &sn, &cs);
     ux = eval(cs, sn, xt, om);
     cst = cs;
     snt = sn;
     omt = om;
-    float pt = ux + fd * amh_logf(om);
-    if (amh_isnan(pt)) pt = INFINITY;
+    const float pt = asss_slice_pt(ux, fd, om);
     iter += 1;
-    cont = (iter < kAsssBigMaxIter) && ((pt > tpe) || (om < eps));
+    cont = (iter < kAsssMaxIter) && ((pt > tpe) || (om < eps));
   }
-  const bool capped = degen || iter >= kAsssBigMaxIter;  // asss.py:94: theta = 0
+  const bool capped = !asss_moved(degen, iter);  // asss.py:94: theta = 0
   if (capped) {
     cst = 1.0f;
     snt = 0.0f;
@@ -835,7 +826,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
         const float t = act ? gw2[K] / Dg[K] : 0.0f;
         const float ex = Grp<64>::excl_scan(t, lane);
         const float bs = (K == 0) ? ex : ex + carry;
-        const float tot = rdl(ex + t, 63);
+        const float tot = rdlane(ex + t, 63);
         carry = (K == 0) ? tot : carry + tot;
         const float bq = 1.0f + bs;
         const float g2 = (bq * Dg[K]) + gw2[K];
@@ -860,8 +851,8 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
       for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
         constexpr int kb = KB;
         const int jl = j - 64 * kb;
-        const float wsj = rdl(ws[kb], jl), cj = rdl(cc[kb], jl), acj = rdl(ac[kb], jl);
-        const float bcj = rdl(bc[kb], jl), invj = rdl(inv[kb], jl), qj = rdl(qq[kb], jl);
+        const float wsj = rdlane(ws[kb], jl), cj = rdlane(cc[kb], jl), acj = rdlane(ac[kb], jl);
+        const float bcj = rdlane(bc[kb], jl), invj = rdlane(inv[kb], jl), qj = rdlane(qq[kb], jl);
         float* ocol = Lout + col_off(d, j) - j;
         if (lane == jl) {
           const float t0 = fmaf(1.0f, acj, bcj * 0.0f);
@@ -1044,7 +1035,7 @@ __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
             static_for<NS>([&](auto K) { pr[T][K] = (kin && 64 * K + lane < d) ? row[64 * K + lane] : 0.0f; });
           });
           static_for<8>([&](auto T) {
-            const float dk = rdl(D[kb], k2 + T);
+            const float dk = rdlane(D[kb], k2 + T);
             static_for<NS>([&](auto K) { Y[K] = fmaf(pr[T][K], dk, Y[K]); });
           });
         }
@@ -1062,8 +1053,8 @@ __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
           static_for<2>([&](auto H) {
             float a = 0.0f;
             static_for<16>([&](auto G) {
-              constexpr int l = 32 * I2 + (G & 3) + 8 * (G >> 2) + 4 * H;
-              a = a + rdl(q[K], l);
+              constexpr int l = mfma_row(G, H, 32 * I2);
+              a = a + rdlane(q[K], l);
             });
             ph[(int)H] = a;
           });
@@ -1090,7 +1081,7 @@ __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
       static_for<NS>([&](auto K) { acc[K] = 0.0f; });
       for_columns<RAG, NS>(p.scale, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
         constexpr int kb = KB;
-        const float xj = rdl(xi[kb], j - 64 * kb);
+        const float xj = rdlane(xi[kb], j - 64 * kb);
         static_for<NS>([&](auto K) {
           if constexpr (K >= kb) {
             const int r = 64 * K + lane;

@@ -39,10 +39,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kLd = 65;          // LDS row stride of [k][chain] tiles
 
-__device__ __forceinline__ float rdlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ int64_t pk(int d, int r, int k) { return col_off(d, k) + (r - k); }
 }  // namespace
 
 // -------------------------------------------------- fused stats, d = 64 --
@@ -328,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
       });
       const int ch = 32 * hf + i;
       static_for<16>([&](auto R) {
-        const int rr = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
+        const int rr = mfma_row(R, h, 32 * T);
         const float v = fmaf(el, acc[(int)R], p.eps * Xi[ch * kFS + fperm(rr)]);
         Xp[ch * kFS + fperm(rr)] = Zs[ch * kFS + rr] + v;  // xprop = z + (e^lam L xi + eps xi)
       });
@@ -352,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
       });
       float ps = 0.0f;
       static_for<16>([&](auto R) {
-        const int row = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
+        const int row = mfma_row(R, h, 32 * T);
         ps = ps + (Xp[ch * kFS + fperm(row)] - mn[row]) * acc[(int)R];
       });
       const float other = __shfl_xor(ps, 32, 64);
@@ -504,7 +500,6 @@ __global__ __launch_bounds__(256, 2) void pooled_fused64_kernel(PooledStatsParam
 // sums).  Float operations and their
 // order: those of orc_pooled_stats_big (the MFMA k order of
 // gauss_pot_mfma_kernel for the potential).
-constexpr int kFB = 128;  // chains per chunk above d = 64 (bit spec)
 constexpr int kFBWaves = 8;
 template <int NT>
 constexpr size_t fused_big_lds_bytes() {
@@ -587,8 +582,7 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
   int sI[NS], sJ[NS];
   static_for<NS>([&](auto S) {
     const int u = w + kFBWaves * S;
-    int I = 0;
-    while ((I + 1) * (I + 2) / 2 <= u) ++I;
+    const int I = tile_pair_row(u);
     sI[S] = (u < NPAIR) ? I : -1;
     sJ[S] = u - I * (I + 1) / 2;
   });
@@ -602,8 +596,8 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
     float sd = 0.0f, sa = 0.0f;
     int cnt = 0;
 #pragma unroll 1
-    for (int half = 0; half < kFB / 64; ++half) {
-      const int64_t c0 = chunk * kFB + 64 * half;
+    for (int half = 0; half < kBigChunk / 64; ++half) {
+      const int64_t c0 = chunk * kBigChunk + 64 * half;
       const int64_t left = p.C - c0;
       if (left <= 0) break;
       const int nv = left < 64 ? (int)left : 64;
@@ -704,7 +698,7 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
             static_for<4>([&](auto KB) { cur[KB] = nxt[KB]; });
           }
           static_for<16>([&](auto R) {
-            const int rr = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
+            const int rr = mfma_row(R, h, 32 * T);
             v0[R] = fmaf(el, acc0[(int)R], p.eps * Xb[rr * kLd + i]);
             v1[R] = fmaf(el, acc1[(int)R], p.eps * Xb[rr * kLd + 32 + i]);
           });
@@ -713,7 +707,7 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
         // xprop = z + (e^lam L xi + eps xi) -> Xb; D = xprop - m -> Zb
         if (pT >= 0) {
           static_for<16>([&](auto R) {
-            const int rr = 32 * pT + (R & 3) + 8 * (R >> 2) + 4 * h;
+            const int rr = mfma_row(R, h, 32 * pT);
             const int o = rr * kLd + i;
             const float xp0 = Zb[o] + v0[R];
             const float xp1 = Zb[o + 32] + v1[R];
@@ -757,7 +751,7 @@ __global__ __launch_bounds__(512) void pooled_fused_big_kernel(PooledStatsParams
         }
         float ps0 = 0.0f, ps1 = 0.0f;
         static_for<16>([&](auto R) {
-          const int row = 32 * T + (R & 3) + 8 * (R >> 2) + 4 * h;
+          const int row = mfma_row(R, h, 32 * T);
           ps0 = ps0 + Zb[row * kLd + i] * acc0[(int)R];
           ps1 = ps1 + Zb[row * kLd + 32 + i] * acc1[(int)R];
         });
@@ -1304,8 +1298,7 @@ __global__ __launch_bounds__(64 * kUpdWaves) void pooled_big_update_kernel(Poole
       const int mt = (d - q0) / 32;
       const int npair1 = mt * (mt - 1) / 2;  // tile pairs with J >= 1
       for (int u = w - nwv; u >= 0 && u < npair1; u += kUpdWaves - nwv) {
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= u) ++I;
+        const int I = tile_pair_row(u);
         trailing_tile(A, d, p0 - 32, q0, I + 1, u - I * (I + 1) / 2 + 1, lane);
       }
     }
@@ -1976,7 +1969,7 @@ __global__ __launch_bounds__(256) void pooled_big_post_kernel(PooledUpdateParams
 // --------------------------------------------------------------- launchers --
 // chains per chunk of the sums (bit spec): 128 at every d >= 64
 int64_t pooled_big_chunks(int64_t C, int d) {
-  const int64_t ch = (d == kF) ? kFChunk : kFB;
+  const int64_t ch = (d == kF) ? kFChunk : kBigChunk;
   return (C + ch - 1) / ch;
 }
 

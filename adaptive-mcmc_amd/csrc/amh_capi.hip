@@ -1242,6 +1242,42 @@ int exact_reduce(amh_handle* h, int64_t n_chunks, bool big, int64_t* acc, int ac
   return AMH_OK;
 }
 
+// The chains and the shared state of `in` as a stats-side kernel's parameters
+// (PooledStatsParams, PooledExtParams): the fields both carry.  The
+// lane-per-row chunks are cut by total_chains (the chains of all ranks under
+// exact sums, else num_chains).
+template <class P>
+P pooled_params(const amh_handle* h, int64_t num_chains, const amh_pooled_state* in, int64_t total_chains) {
+  P p{};
+  p.C = num_chains;
+  p.cpw = amh::pooled_cpw(total_chains);
+  p.d = h->cfg.dim;
+  p.i = in->i;
+  p.z = in->z;
+  p.pe = in->potential_energy;
+  p.keys = in->rng_key;
+  p.mu = in->loc;
+  p.L = in->scale;
+  p.lam = in->log_step_size;
+  p.eps = h->cfg.eps;
+  return p;
+}
+
+// ... and the update's, from the handle's adaptation settings
+amh::PooledUpdateParams pooled_update_params(const amh_handle* h, const double* sums, const amh_pooled_state* in,
+                                             const amh_pooled_state* out, int32_t k_steps) {
+  amh::PooledUpdateParams p{};
+  p.d = h->cfg.dim;
+  p.W = h->cfg.num_warmup;
+  p.a = h->cfg.lr_decay;
+  p.target = h->cfg.target_accept_prob;
+  p.sums = sums;
+  p.in = *in;
+  p.out = *out;
+  p.K = k_steps;
+  return p;
+}
+
 // prep_for_update: the update follows in the same library call with no
 // exchange in between (amh_pooled_step_k on one rank), so the large-d
 // reduction's last kernel also forms that update's Sigma'.
@@ -1277,18 +1313,7 @@ int pooled_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_state*
   const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
   const int64_t n_chunks = big ? amh::pooled_big_chunks(num_chains, d) : (num_chains + chunk - 1) / chunk;
   if (int rc = reserve_partials(h, n_chunks, big, stream, who)) return rc;
-  amh::PooledStatsParams p{};
-  p.C = num_chains;
-  p.cpw = cpw;
-  p.d = d;
-  p.i = in->i;
-  p.z = in->z;
-  p.pe = in->potential_energy;
-  p.keys = in->rng_key;
-  p.mu = in->loc;
-  p.L = in->scale;
-  p.lam = in->log_step_size;
-  p.eps = h->cfg.eps;
+  amh::PooledStatsParams p = pooled_params<amh::PooledStatsParams>(h, num_chains, in, total_chains);
   p.z_out = z_out;
   p.pe_out = pe_out;
   p.partials = h->partials.as<double>();
@@ -1367,15 +1392,7 @@ int pooled_update_impl(amh_handle* h, const double* sums, const amh_pooled_state
     return fail(h, AMH_EINVAL, "amh_pooled_update: d > 64 needs d % 32 == 0 in the pooled mode");
   if (int rc = check_device_flag(h)) return rc;
   if (int rc = use_device(h, who)) return rc;
-  amh::PooledUpdateParams p{};
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.sums = sums;
-  p.in = *in;
-  p.out = *out;
-  p.K = k_steps;
+  amh::PooledUpdateParams p = pooled_update_params(h, sums, in, out, k_steps);
   hipError_t e;
   if (amh::pooled_big_model(h->model_id, p.d)) {
     if (int rc = reserve_update_scratch(h, stream, who)) return rc;
@@ -1424,19 +1441,8 @@ int pooled_ext_params(amh_handle* h, int64_t num_chains, const amh_pooled_state*
   if (d > 64 && !amh::pooled_big_model(h->model_id, d))
     return fail(h, AMH_EINVAL, std::string(who) + ": d > 64 needs d % 32 == 0 in the pooled mode");
   if (!pooled_ok(in) || num_chains < 1 || t < 0) return fail(h, AMH_EINVAL, std::string(who) + ": bad arguments");
-  *p = amh::PooledExtParams{};
-  p->C = num_chains;
-  p->d = d;
-  p->i = in->i;
+  *p = pooled_params<amh::PooledExtParams>(h, num_chains, in, num_chains);
   p->t = t;
-  p->z = in->z;
-  p->pe = in->potential_energy;
-  p->keys = in->rng_key;
-  p->mu = in->loc;
-  p->L = in->scale;
-  p->lam = in->log_step_size;
-  p->eps = h->cfg.eps;
-  p->cpw = amh::pooled_cpw(num_chains);
   return AMH_OK;
 }
 
@@ -1675,17 +1681,7 @@ int pooled_asss_stats_impl(amh_handle* h, int64_t num_chains, const amh_pooled_s
   const int64_t chunk = (int64_t)amh::kPoolWaves * cpw;
   const int64_t n_chunks = (num_chains + chunk - 1) / chunk;
   if (int rc = reserve_partials(h, n_chunks, false, stream, who)) return rc;
-  amh::PooledStatsParams p{};
-  p.C = num_chains;
-  p.cpw = cpw;
-  p.d = h->cfg.dim;
-  p.i = in->i;
-  p.z = in->z;
-  p.pe = in->potential_energy;
-  p.keys = in->rng_key;
-  p.mu = in->loc;
-  p.L = in->scale;
-  p.eps = h->cfg.eps;
+  amh::PooledStatsParams p = pooled_params<amh::PooledStatsParams>(h, num_chains, in, num_chains);
   p.z_out = z_out;
   p.pe_out = pe_out;
   p.partials = h->partials.as<double>();
@@ -1702,15 +1698,7 @@ int pooled_asss_update_impl(amh_handle* h, const double* sums, const amh_pooled_
   if (k_steps < 1 || h->cfg.num_warmup % k_steps != 0)
     return fail(h, AMH_EINVAL, std::string(who) + ": k_steps must be >= 1 and divide num_warmup");
   if (int rc = use_device(h, who)) return rc;
-  amh::PooledUpdateParams p{};
-  p.d = h->cfg.dim;
-  p.W = h->cfg.num_warmup;
-  p.a = h->cfg.lr_decay;
-  p.target = h->cfg.target_accept_prob;
-  p.sums = sums;
-  p.in = *in;
-  p.out = *out;
-  p.K = k_steps;
+  const amh::PooledUpdateParams p = pooled_update_params(h, sums, in, out, k_steps);
   const hipError_t e = amh::run_pooled_update(p, (hipStream_t)stream, true);
   if (e != hipSuccess) return hip_fail(h, e, who);
   return AMH_OK;

@@ -289,6 +289,28 @@ __device__ __forceinline__ uint32_t off_from(uint32_t v, uint32_t oob, int rr) {
 __device__ __forceinline__ int64_t col_off(int d, int j) {
   return (int64_t)j * d - (int64_t)j * (j - 1) / 2;
 }
+// ... and element (r, k), r >= k, of it
+__device__ __forceinline__ int64_t pk(int d, int r, int k) { return col_off(d, k) + (r - k); }
+
+// row of accumulator register R in lane half h of a 32x32 MFMA tile whose
+// first row is row0
+__host__ __device__ __forceinline__ constexpr int mfma_row(const int& R, const int& h, const int& row0 = 0) {
+  return row0 + (R & 3) + 8 * (R >> 2) + 4 * h;
+}
+
+// pair u = I (I + 1) / 2 + J, J <= I, of the lower triangle's 32x32 tiles -> I
+__host__ __device__ __forceinline__ int tile_pair_row(const int& u) {
+  int I = 0;
+  while ((I + 1) * (I + 2) / 2 <= u) ++I;
+  return I;
+}
+
+// lane l's v, l wave-uniform
+__device__ __forceinline__ float rdlane(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+constexpr int kBigChunk = 128;  // chains per chunk of the pooled sums from d = 64 up (bit spec)
 
 #define HALF_LOG_2PI 0.918938533204672742f
 
@@ -992,10 +1014,9 @@ __device__ inline int64_t tile_to_packed(int64_t u, int64_t Vt, int d, int* prow
   if (u >= Vt - 4) return -1;  // padding (V % 4 == 0)
   const int64_t q = u - d;
   const int pair = (int)(q >> 10), R = (int)((q >> 6) & 15), lane = (int)(q & 63);
-  int I = 0;
-  while ((I + 1) * (I + 2) / 2 <= pair) ++I;
+  const int I = tile_pair_row(pair);
   const int J = pair - I * (I + 1) / 2;
-  const int row = 32 * I + (R & 3) + 8 * (R >> 2) + 4 * (lane >> 5), col = 32 * J + (lane & 31);
+  const int row = mfma_row(R, lane >> 5, 32 * I), col = 32 * J + (lane & 31);
   if (row < col) return -1;
   if (prow) *prow = row;
   if (pcol) *pcol = col;

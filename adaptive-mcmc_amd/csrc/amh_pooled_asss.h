@@ -4,7 +4,8 @@
 // potential behind them, the begin kernel around a caller's potential
 // (amh_pooled_asss_ext.hip) runs them and stops where the first U is needed.
 // A wave owns the chain, lane r = coordinate r, G = 64 at every d; the draws,
-// the tangent and the circle's points are amh_asss.h's own pieces at G = 64.
+// the tangent, the circle's points and the slice walk (the fused transition)
+// are amh_asss.h's own pieces at G = 64.
 #pragma once
 #include "amh_asss.h"
 #include "amh_pooled_device.h"

@@ -12,8 +12,9 @@
 //   (S z [d], S v [d], mu [d] -- the shared mu copied per chain -- and the
 //   scalars kZd .. kKey1 of amh_asss.h)
 //   pooled_asss_ext_finish_kernel  the outcome (asss_outcome), z' / pe' out, and
-//                                  the transition's pooled sums in the chunk
-//                                  geometry of pooled_asss_stats_kernel, so that
+//                                  the transition's pooled sums on the chunk
+//                                  scaffold of pooled_asss_stats_kernel
+//                                  (pooled_chunk_walk), so that
 //                                  one transition's sums are that kernel's at
 //                                  k_steps = 1 byte for byte
 //
@@ -85,91 +86,48 @@ __global__ __launch_bounds__(kPoolWaves * 64) void pooled_asss_ext_begin_kernel(
       wk[d + r] = Sv;
       wk[2 * d + r] = sh.mu;
     }
-    if (r == 0) {
-      float* sc = wk + 3 * d;
-      int32_t* si = (int32_t*)sc;
-      sc[kZd] = zd;
-      sc[kVd] = vd;
-      sc[kTh] = th0;
-      sc[kThmin] = th0 - 6.28318548f;
-      sc[kThmax] = th0;
-      si[kIter] = 0;
-      sc[kUt] = ut;
-      sc[kOm0] = om0;
-      sc[kOm] = om;
-      si[kDegen] = degen ? 1 : 0;
-      si[kCont] = 1;
-      sc[kTpe] = 0.0f;
-      sc[kU0] = 0.0f;
-      sc[kUx] = 0.0f;
-      si[kIt] = it;
-      si[kKey0] = (int32_t)k0;
-      si[kKey1] = (int32_t)k1;
-    }
+    if (r == 0) asss_ext_record_init(wk + 3 * d, zd, vd, th0, ut, om0, om, degen, it, k0, k1);
   }
 }
 
 // ----------------------------------------------------------------- finish ----
 // The chunk layout of pooled_asss_stats_kernel: block b is chunk b, wave w
 // takes its chains [b 16 cpw + w cpw, + cpw) in order (pooled_ext_stats_kernel
-// with asss_outcome in place of accept).  The next chain's candidates and
-// record are loaded while the current one is accumulated.
+// with asss_outcome in place of accept), on pooled_chunk_walk: the next chain's
+// candidates and record are loaded while the current one is accumulated.
 template <bool EXACT>
 __global__ __launch_bounds__(kPoolWaves * 64) void pooled_asss_ext_finish_kernel(PooledAsssExtParams q) {
   extern __shared__ float tree[];
   const PooledExtParams& p = q.sp;
   const int d = EXACT ? 64 : p.d;
   const int64_t C = p.C;
-  const int64_t V = pooled_sums_len(d);
   const int64_t WS = asss_ext_work_floats(d);
   const int r = lane_id();
   const bool act = r < d;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
   const float mu = act ? p.mu[r] : 0.0f;
 
-  const int cpw = p.cpw;
-  const int64_t chunk0 = (int64_t)blockIdx.x * kPoolWaves * cpw;
-  const int64_t base = chunk0 + (int64_t)w * cpw;
-  const int64_t end = (base + cpw < C) ? base + cpw : C;
-  float S[64];
-  static_for<64>([&](auto K) { S[K] = 0.0f; });
-  float sd = 0.0f, sa = 0.0f;
-  const uint32_t vr = 4u * (uint32_t)r;
-  const uint32_t row = 4u * (uint32_t)d;
-  auto load_chain = [&](int64_t c, float& x0, float& xt, int32_t& dg, int32_t& iter, float& U0, float& ux) {
-    const Buf b0(uniform_ptr(q.cand + c * d), row);
-    const Buf b1(uniform_ptr(q.cand + (C + c) * d), row);
-    x0 = b0.ld(vr, 0);
-    xt = b1.ld(vr, 0);
-    const float* sc = q.work + c * WS + 3 * d;
-    const int32_t* si = (const int32_t*)sc;
-    dg = si[kDegen];
-    iter = si[kIter];
-    U0 = sc[kU0];
-    ux = sc[kUx];
+  // a chain's state is the point at theta = 0 and its U until the outcome
+  struct Q {
+    float z, pe, xt, ux;
+    int32_t degen, iter;
   };
-  float x0q = 0.0f, xtq = 0.0f, U0q = 0.0f, uxq = 0.0f;
-  int32_t dgq = 0, iterq = 0;
-  if (base < end) load_chain(base, x0q, xtq, dgq, iterq, U0q, uxq);
-  for (int64_t c = base; c < end; ++c) {
-    const float x0 = x0q, xt = xtq, U0 = U0q, ux = uxq;
-    const int32_t dg = dgq, iter = iterq;
-    if (c + 1 < end) load_chain(c + 1, x0q, xtq, dgq, iterq, U0q, uxq);
-    float z, pe;
-    asss_outcome(dg != 0, iter, x0, xt, U0, ux, z, pe);
-    const bool moved = !(dg != 0 || iter >= kAsssMaxIter);
-    // pooled statistics, in the order of pooled_asss_stats_kernel
-    const float delta = act ? z - mu : 0.0f;
-    pooled_accumulate(S, sd, delta, d);
-    sa = sa + (moved ? 1.0f : 0.0f);
-    const Buf bo(uniform_ptr(p.z_out + c * d), row);
-    bo.st(z, vr, 0);
-    if (r == 0) p.pe_out[c] = pe;
-  }
-  const int64_t left = C - chunk0;
-  const int64_t full = (int64_t)kPoolWaves * cpw;
-  pooled_chunk_out(S, sd, sa, tree, r, act, w, d, p.partials + (int64_t)blockIdx.x * V,
-                   (double)(left < full ? left : full));
+  pooled_chunk_walk<Q>(
+      p, d, 1, mu, r, act, w, tree,
+      [&](const WaveRows& rows, int64_t c, Q& n) __attribute__((always_inline)) {
+        n.z = rows.ld(q.cand, c);
+        n.xt = rows.ld(q.cand, C + c);
+        const float* sc = q.work + c * WS + 3 * d;
+        const int32_t* si = (const int32_t*)sc;
+        n.degen = si[kDegen];
+        n.iter = si[kIter];
+        n.pe = sc[kU0];
+        n.ux = sc[kUx];
+      },
+      [&](const Q& n, int, float& z, float& pe) __attribute__((always_inline)) {
+        asss_outcome(n.degen != 0, n.iter, n.z, n.xt, n.pe, n.ux, z, pe);
+        return asss_moved(n.degen != 0, n.iter) ? 1.0f : 0.0f;
+      });
 }
 
 // -------------------------------------------------------------- launchers ----

@@ -1,9 +1,11 @@
 // amh_pooled_device.h -- device pieces of the pooled mode's lane-per-row form
 // (d < 64, and the d = 64 registry models off the MFMA path) shared by the
-// fused kernel (amh_pooled.hip) and the kernels split around the caller's
-// potential (amh_pooled_ext.hip): the shared factor's row dot from LDS, a
-// chain-step's contribution to the wave's sums, and the chunk's combine tree.
-// Every order here is part of the bit spec (oracle: orc_pooled_stats_k).
+// fused kernels (amh_pooled.hip, amh_pooled_asss.hip) and the kernels split
+// around the caller's potential (amh_pooled_ext.hip, amh_pooled_asss_ext.hip):
+// the shared factor's row dot from LDS, a chain-step's contribution to the
+// wave's sums, the chunk's combine tree, and the chunk scaffold around them
+// (PooledChunk, pooled_chunk_walk).  Every order here is part of the bit spec
+// (oracle: orc_pooled_stats_k).
 #pragma once
 #include "amh_device.h"
 
@@ -143,6 +145,93 @@ __device__ __forceinline__ void pooled_chunk_out(float (&S)[64], float sd, float
       out[d + P + 1] = count;
     }
   }
+}
+
+// Row c of a [C][d] array as the wave sees it, lane r = coordinate r, through
+// a buffer descriptor with a wave-uniform base: no 64-bit per-lane addresses
+// to keep live, lanes r >= d read 0 / store nothing.
+struct WaveRows {
+  int d;
+  uint32_t vr, bytes;
+  __device__ __forceinline__ WaveRows(const int& d_, const int& r) : d(d_), vr(4u * (uint32_t)r), bytes(4u * (uint32_t)d_) {}
+  __device__ __forceinline__ float ld(const float* a, const int64_t& c) const {
+    return Buf(uniform_ptr(a + c * d), bytes).ld(vr, 0);
+  }
+  __device__ __forceinline__ void st(float* a, const int64_t& c, const float& v) const {
+    Buf(uniform_ptr(a + c * d), bytes).st(v, vr, 0);
+  }
+};
+
+// The chunk scaffold of the lane-per-row stats kernels, as pooled_stats_kernel
+// (amh_pooled.hip) and pooled_ext_stats_kernel (amh_pooled_ext.hip) write it
+// out and pooled_asss_stats_kernel and pooled_asss_ext_finish_kernel take it
+// from here: block b is chunk b, wave w takes its chains [base, end) = [b 16 cpw + w cpw,
+// + cpw) in order, adds every chain-step to its float32 sums and stores the
+// chain; the sums leave through pooled_chunk_out with N = K * the chunk's
+// chains.  `p` (PooledStatsParams / PooledExtParams) gives C, cpw, z_out,
+// pe_out and partials.  The order of the chains, and of a chain's steps, is
+// part of the bit spec.  (Scalars come by reference throughout: these kernels
+// run 1024-thread blocks at the 128-VGPR cap, and a by-value copy at an inlined
+// call moves their register allocation.)
+struct PooledChunk {
+  int64_t chunk0, base, end;
+  float S[64], sd, sa;
+  WaveRows rows;
+  template <class Params>
+  __device__ __forceinline__ PooledChunk(const Params& p, const int& d, const int& r, const int& w)
+      : chunk0((int64_t)blockIdx.x * kPoolWaves * p.cpw), base(chunk0 + (int64_t)w * p.cpw), rows(d, r) {
+    static_for<64>([&](auto J) { S[J] = 0.0f; });
+    sd = sa = 0.0f;
+    end = (base + p.cpw < p.C) ? base + p.cpw : p.C;
+  }
+  // one chain-step: the state z after it and its share `a` of S_a
+  __device__ __forceinline__ void add(const float& z, const float& mu, const float& a, const bool& act, const int& d) {
+    const float delta = act ? z - mu : 0.0f;
+    pooled_accumulate(S, sd, delta, d);
+    sa = sa + a;
+  }
+  // chain c after its steps
+  template <class Params>
+  __device__ __forceinline__ void store(const Params& p, const int64_t& c, const float& z, const float& pe, const int& r) const {
+    rows.st(p.z_out, c, z);
+    if (r == 0) p.pe_out[c] = pe;
+  }
+  // the 16 wave partials -> the chunk's partial row (fixed float32 tree, then
+  // double), K steps per chain.  Block-wide: every wave calls it.
+  template <class Params>
+  __device__ __forceinline__ void out(const Params& p, float* tree, const int& K, const int& r, const bool& act, const int& w,
+                                  const int& d) {
+    const int64_t left = p.C - chunk0;
+    const int64_t full = (int64_t)kPoolWaves * p.cpw;
+    pooled_chunk_out(S, sd, sa, tree, r, act, w, d, p.partials + (int64_t)blockIdx.x * pooled_sums_len(d),
+                     (double)K * (double)(left < full ? left : full));
+  }
+};
+
+// The whole scaffold around two callables, per chain
+//   load(rows, c, q)    fetches what chain c needs into q, a Q whose z / pe are
+//                       the chain's state; it runs one chain ahead, while the
+//                       current chain is computed
+//   step(q, t, z, pe)   step t < K of the chain: replaces z / pe and returns the
+//                       step's share of S_a
+template <class Q, class Params, class Load, class Step>
+__device__ __forceinline__ void pooled_chunk_walk(const Params& p, const int& d, const int& K, const float& mu,
+                                                  const int& r, const bool& act, const int& w, float* tree,
+                                                  Load&& load, Step&& step) {
+  PooledChunk ck(p, d, r, w);
+  Q nxt{};
+  if (ck.base < ck.end) load(ck.rows, ck.base, nxt);
+  for (int64_t c = ck.base; c < ck.end; ++c) {
+    const Q cur = nxt;
+    if (c + 1 < ck.end) load(ck.rows, c + 1, nxt);
+    float z = cur.z, pe = cur.pe;
+    for (int t = 0; t < K; ++t) {
+      const float a = step(cur, t, z, pe);
+      ck.add(z, mu, a, act, d);
+    }
+    ck.store(p, c, z, pe, r);
+  }
+  ck.out(p, tree, K, r, act, w, d);
 }
 
 }  // namespace amh

@@ -30,12 +30,8 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kLd = 65;        // LDS row stride of [k][chain] tiles
 constexpr int kTile = 64;      // chains per proposal tile / stats half
-constexpr int kChunk = 128;    // chains per chunk of the sums from d = 64 up (bit spec)
 constexpr int kPropWaves = 4;  // waves of the MFMA proposal block
 constexpr int kStatWaves = 8;  // waves of the MFMA stats block
-__device__ __forceinline__ int64_t pk(int d, int r, int k) { return col_off(d, k) + (r - k); }
-// row of accumulator register R in lane half h of a 32x32 MFMA tile
-__device__ __forceinline__ int mfma_row(int R, int h) { return (R & 3) + 8 * (R >> 2) + 4 * h; }
 }  // namespace
 
 // ---------------------------------------------------------------- d < 64 --
@@ -248,8 +244,7 @@ __global__ __launch_bounds__(64 * kStatWaves) void pooled_ext_stats_big_kernel(P
   int sI[NS], sJ[NS];
   static_for<NS>([&](auto S) {
     const int u = w + kStatWaves * S;
-    int I = 0;
-    while ((I + 1) * (I + 2) / 2 <= u) ++I;
+    const int I = tile_pair_row(u);
     sI[S] = (u < NPAIR) ? I : -1;
     sJ[S] = u - I * (I + 1) / 2;
   });
@@ -261,8 +256,8 @@ __global__ __launch_bounds__(64 * kStatWaves) void pooled_ext_stats_big_kernel(P
     float sd = 0.0f, sa = 0.0f;
     int cnt = 0;
 #pragma unroll 1
-    for (int half = 0; half < kChunk / kTile; ++half) {
-      const int64_t c0 = chunk * kChunk + (int64_t)kTile * half;
+    for (int half = 0; half < kBigChunk / kTile; ++half) {
+      const int64_t c0 = chunk * kBigChunk + (int64_t)kTile * half;
       const int64_t left = p.C - c0;
       if (left <= 0) break;  // block-uniform
       const int nv = left < kTile ? (int)left : kTile;
@@ -393,7 +388,7 @@ hipError_t run_pooled_ext_propose(const PooledExtParams& p, hipStream_t s) {
 }
 
 int64_t pooled_ext_chunks(int64_t C, int d, int cpw) {
-  if (ext_big(d)) return (C + kChunk - 1) / kChunk;
+  if (ext_big(d)) return (C + kBigChunk - 1) / kBigChunk;
   const int64_t chunk = (int64_t)kPoolWaves * cpw;
   return (C + chunk - 1) / chunk;
 }

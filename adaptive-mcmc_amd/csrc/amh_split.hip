@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256, (NB == 2 ? 2 : 1)) void diamonds_pot_mfma_kern
     });
     const int64_t nrem = N - 32 * m;  // rows of this tile that exist
     static_for<16>([&](auto R) {
-      const int rr = (R & 3) + 8 * (R >> 2) + 4 * h;
+      const int rr = mfma_row(R, h);
       const float yv = y[R / 4][R % 4];
       static_for<NB>([&](auto J) {
         const float e = (yv - (icq[J] + acc[J][(int)R])) * isq[J];
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256, (NB == 2 ? 2 : 1)) void diamonds_pot_mfma_kern
     static_for<16>([&](auto R) {
       const float mine = h ? part[P1][R] : part[P0][R];
       const float other = __shfl_xor(h ? part[P0][R] : part[P1][R], 32, 64);
-      const int rm = (R & 3) + 8 * (R >> 2);
+      const int rm = mfma_row(R, 0);
       if (h == 0) {
         all[rm] = mine;
         all[rm + 4] = other;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void glm_pack_kernel(const float* __restrict__
   }
   if (t >= 256 - 32 * nside) {
     const int q = t - (256 - 32 * nside), which = q >> 5, h = (q >> 4) & 1, R = q & 15;
-    const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;
+    const int64_t row = 32 * m + (R & 3) + 8 * (R >> 2) + 4 * h;  // mfma_row in the 64-bit row index
     xp[NT * GV * 256 + 32 * nside * m + q] = row < N ? side[which * N + row] : 0.0f;
   }
 }
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void glm_pot_mfma_kernel(PotParams p) {
     });
     const int64_t nrem = N - 32 * m;  // rows of this tile that exist
     static_for<16>([&](auto R) {
-      const int rr = (R & 3) + 8 * (R >> 2) + 4 * h;
+      const int rr = mfma_row(R, h);
       float sv[NSIDE];
       static_for<NSIDE>([&](auto V) { sv[V] = sd[V][R / 4][R % 4]; });
       static_for<NB>([&](auto J) {
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void glm_pot_mfma_kernel(PotParams p) {
     static_for<16>([&](auto R) {
       const float mine = h ? part[P1][R] : part[P0][R];
       const float other = __shfl_xor(h ? part[P0][R] : part[P1][R], 32, 64);
-      const int rm = (R & 3) + 8 * (R >> 2);
+      const int rm = mfma_row(R, 0);
       if (h == 0) {
         all[rm] = mine;
         all[rm + 4] = other;

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import pooled_asss_bits as bits
 import pooled_asss_np as pa
 import pooled_np as pnp
 from helpers import apply_shared, make_case, shared_to_host
@@ -133,6 +134,29 @@ def test_pooled_asss_against_float64(kind, d, C, K, gpu):
             assert np.array_equal(pa.lane_sum_bound(A_dd, d, C, K), pnp.bounds.S_dd(A_dd, d, C, K))
         # ---- update from the kernel's own sums
         _check_update(before, shared_to_host(st), sums, d, K)
+
+
+@pytest.fixture(scope="module")
+def recorded_bits():
+    return np.load(bits.PATH)
+
+
+@pytest.mark.parametrize("kind,d,C,K", bits.CASES)
+def test_fused_blocks_equal_the_recorded_bits(kind, d, C, K, gpu, recorded_bits):
+    """Three blocks from init (PRNGKey(7), num_warmup = 4) against
+    tests/golden/pooled_asss_bits.npz, byte for byte: per block the sums, the
+    shared leaves and pe, and z after the last block.  The fixture was recorded
+    (tests/golden/make_pooled_asss_bits.py) with the build before the fused
+    transition and its external twin came to share the slice walk and the
+    chunk scaffold, which their mutual byte equality no longer sees into."""
+    got = bits.run(kind, d, C, K)
+    prefix = bits.case_id(kind, d, C, K) + "/"
+    names = [n[len(prefix):] for n in recorded_bits.files if n.startswith(prefix)]
+    assert sorted(names) == sorted(got) and len(names) == 1 + bits.BLOCKS * 9
+    for name in names:
+        ref = recorded_bits[prefix + name]
+        assert got[name].dtype == ref.dtype and got[name].shape == ref.shape, name
+        assert got[name].tobytes() == ref.tobytes(), name
 
 
 def _gauss_pair(d, C, K, gpu, seed=1, **opts):

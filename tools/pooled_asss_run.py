@@ -19,10 +19,14 @@ transitions each (HIP events): seconds per transition (median, min - max), the
 mean and maximum shrink rounds per transition, and the ratio.
 
 python3 tools/pooled_asss_run.py legs [N]
-The two legs an A/B of two builds compares (select the build with
-AMH_LIB_PATH): the fused PooledASSS step at d = 64, C = 65,536, K = 1 and the
-per-chain ASSS(host_shrink=True) step at d = 64, C = 512 around the library's
-potential; one JSON line with us per transition of each."""
+The legs an A/B of two builds compares (select the build with AMH_LIB_PATH):
+the fused PooledASSS step at d = 64, C = 65,536, K = 1 and at eight schools,
+C = 262,144; the per-chain ASSS(host_shrink=True) step at d = 64, C = 512
+around the library's potential; the lane-per-row PooledARWMH step at d = 63,
+C = 65,536 and at eight schools, C = 262,144; and, around the library's
+potential behind a callable at C = 65,536, the PooledARWMH step at d = 63
+(pooled_ext_stats_kernel) and the PooledASSS(host_shrink=True) step at d = 64
+(pooled_asss_ext_finish_kernel); one JSON line with us per transition of each."""
 import json
 import os
 import sys
@@ -141,16 +145,29 @@ def external():
 
 def legs():
     d = 64
+    out = {}
+
+    def leg(name, k, st, warm, n):
+        k.sample_(st, warm)
+        out[name] = sorted(timed(lambda: k.sample_(st, 1), n) for _ in range(3))[1]
+
+    def start(C, dim):
+        return (torch.rand(C, dim, device="cuda") * 4 - 2).contiguous()
+
     kf = PooledASSS(potential_fn=P.correlated_gaussian(d), num_chains=65536)
-    sf = kf.init(PRNGKey(0), 0, (torch.rand(65536, d, device="cuda") * 4 - 2).contiguous(), (), {})
-    kf.sample_(sf, 20)
+    leg("pooled_asss_fused_us", kf, kf.init(PRNGKey(0), 0, start(65536, d), (), {}), 20, 4 * N)
     ka = ASSS(potential_fn=library_potential(d), num_chains=512, host_shrink=True)
-    sa = ka.init(PRNGKey(0), 0, (torch.rand(512, d, device="cuda") * 4 - 2).contiguous(), (), {})
-    ka.sample_(sa, 100)
-    tf = sorted(timed(lambda: kf.sample_(sf, 1), 4 * N) for _ in range(3))
-    ta = sorted(timed(lambda: ka.sample_(sa, 1), N) for _ in range(3))
-    print(json.dumps(dict(mode="legs", lib=os.environ.get("AMH_LIB_PATH", "release"), n=N,
-                          pooled_asss_fused_us=tf[1], asss_host_shrink_us=ta[1])))
+    leg("asss_host_shrink_us", ka, ka.init(PRNGKey(0), 0, start(512, d), (), {}), 100, N)
+    for name, cls in (("pooled_asss_es_us", PooledASSS), ("pooled_arwmh_es_us", PooledARWMH)):
+        k, st = make(cls, "eight_schools", 262144, 1)
+        leg(name, k, st, 20, 4 * N)
+    k, st = make(PooledARWMH, "d63", 65536, 1)
+    leg("pooled_arwmh_d63_us", k, st, 20, 4 * N)
+    ke = PooledARWMH(potential_fn=library_potential(63), num_chains=65536)
+    leg("pooled_arwmh_ext_d63_us", ke, ke.init(PRNGKey(0), 0, start(65536, 63), (), {}), 20, N)
+    kh = PooledASSS(potential_fn=library_potential(d), num_chains=65536, host_shrink=True)
+    leg("pooled_asss_ext_us", kh, kh.init(PRNGKey(0), 0, start(65536, d), (), {}), 20, N)
+    print(json.dumps(dict(mode="legs", lib=os.environ.get("AMH_LIB_PATH", "release"), n=N, **out)))
 
 
 if __name__ == "__main__":
