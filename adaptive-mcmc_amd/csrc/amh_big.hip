@@ -27,6 +27,8 @@
 // count is one read and one write); the passes stream it with coalesced
 // column accesses and keep nothing but O(d) per chain on chip.
 // Bit spec: oracle/amh_oracle.c, "large dimensions".
+#include <type_traits>
+
 #include "amh_asss.h"
 #include "amh_device.h"
 
@@ -37,10 +39,9 @@ namespace {
 constexpr int kNSMAX = 4;  // row slots per lane: d <= 64 * NS, NS = 2 (d <= 128) or 4
 
 // gamma_n (scalar cache table, as the step kernel)
-__device__ __forceinline__ float big_gamma(const BigParams& p, int32_t n) {
+__device__ __forceinline__ float big_gamma(const float* gamma_tab, int32_t gamma_tab_n, float a, int32_t n) {
   typedef __attribute__((address_space(4))) const float cf;
-  const cf* tab = (const cf*)p.gamma_tab;
-  return (n < p.gamma_tab_n) ? tab[n] : amh_lr_gamma(n, p.a);
+  return (n < gamma_tab_n) ? ((const cf*)gamma_tab)[n] : amh_lr_gamma(n, a);
 }
 
 // sum over rows: 64-lane butterfly per slot, then (s0 + s1) + (s2 + s3)
@@ -145,6 +146,161 @@ __device__ __forceinline__ void for_columns(const float* Lc, int d, int64_t P, f
   });
 }
 
+// ---- the pieces the streaming kernels share, one copy each ----
+// a wave's share of a 256-thread block: its two LDS column buffers, the packed
+// size of a factor and the number of waves in the grid
+struct BigWave {
+  float *wb0, *wb1;
+  int64_t P, nw;
+};
+__device__ __forceinline__ BigWave big_wave(int d) {
+  extern __shared__ float lds_big[];
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
+  return {wb0, wb0 + kColBlk * d, (int64_t)d * (d + 1) / 2, (int64_t)gridDim.x * 4};
+}
+
+// the factor's diagonal by row slot, and 1 / L_rr (0 for a zero or non-finite one and past d)
+__device__ __forceinline__ float big_inv(float dl) { return (amh_isfinite(dl) && dl != 0.0f) ? 1.0f / dl : 0.0f; }
+template <int NS>
+__device__ __forceinline__ void big_diag(const float* Lc, int d, int lane, float (&dl)[NS], float (&inv)[NS]) {
+  static_for<NS>([&](auto K) {
+    const int r = 64 * K + lane;
+    const bool act = r < d;
+    dl[K] = act ? Lc[col_off(d, act ? r : 0)] : 0.0f;
+    inv[K] = big_inv(dl[K]);
+  });
+}
+
+// Column j of the update inside for_columns (v: column j of L): rows > j of
+// L' go to Lout and to nv, the diagonal q_j to Lout, and sacc gathers
+// ||L' e1 - L e0||_F^2 through ac = q e1 - L_jj e0 and bc = c q e1 (ASSS has no
+// step size: e1 = e0 = 1).  sv is the running solve U^-1 delta of the rows below.
+template <int kb, int NS>
+__device__ __forceinline__ void big_update_column(const int& j, const float (&v)[NS], const float (&ws)[NS],
+                                                  const float (&cc)[NS], const float (&qq)[NS], const float (&ac)[NS],
+                                                  const float (&bc)[NS], const float (&inv)[NS],
+                                                  const float (&delta)[NS], float (&sv)[NS], float (&sacc)[NS],
+                                                  float* Lout, const int& d, const int& lane, float (&nv)[NS]) {
+  const int jl = j - 64 * kb;
+  const float wsj = rdlane(ws[kb], jl), cj = rdlane(cc[kb], jl), acj = rdlane(ac[kb], jl);
+  const float bcj = rdlane(bc[kb], jl), invj = rdlane(inv[kb], jl), qj = rdlane(qq[kb], jl);
+  float* ocol = Lout + col_off(d, j) - j;
+  if (lane == jl) {
+    const float tt = fmaf(1.0f, acj, bcj * 0.0f);
+    sacc[kb] = fmaf(tt, tt, sacc[kb]);
+    ocol[j] = 1.0f * qj;
+  }
+  static_for<NS>([&](auto K) {
+    nv[K] = 0.0f;
+    if constexpr (K >= kb) {
+      const int r = 64 * K + lane;
+      if (r > j && r < d) {
+        const float uo = v[K] * invj;
+        sv[K] = fmaf(uo, wsj, sv[K]);
+        const float w = delta[K] - sv[K];
+        const float un = fmaf(cj, w, uo);
+        const float tt = fmaf(uo, acj, bcj * w);
+        sacc[K] = fmaf(tt, tt, sacc[K]);
+        nv[K] = un * qj;
+        ocol[r] = nv[K];
+      }
+    }
+  });
+}
+
+// The propose pass over a factor's columns in order: z' = z + (L e^lam + eps I)
+// xi and both forward solves of the rank-one update, wa = U^-1 (z' - mu) and
+// wr = U^-1 (z - mu) (U = L D^-1; row j is complete at column j).
+// big_propose_kernel runs it over the stored factor, big_step_kernel<NEXT>
+// over the columns of L' as it forms them.
+template <int NS>
+struct BigPropose {
+  float dg[NS], xi[NS], inv[NS], eta[NS], acc[NS], sa[NS], sr[NS], zp[NS], wa[NS], wr[NS];
+
+  // dg (the diagonal), inv (its inverse) and xi are set
+  __device__ __forceinline__ void begin() {
+    static_for<NS>([&](auto K) {
+      eta[K] = dg[K] * xi[K];
+      acc[K] = sa[K] = sr[K] = zp[K] = wa[K] = wr[K] = 0.0f;
+    });
+  }
+  // The for_columns callable f(KB, j, v): column j (rows > j in v) into the
+  // proposal from (z, mu) and both solves.  The arrays are captured one by
+  // one, as a lambda written in the kernel captures them: with one pointer to
+  // the whole state the aligned propose kernels unroll further and take up to
+  // 11 more VGPRs.
+  __device__ __forceinline__ auto column(const float (&z)[NS], const float (&mu)[NS], const float& el,
+                                         const float& eps, const int& d, const int& lane) {
+    return [&xi = xi, &inv = inv, &eta = eta, &acc = acc, &sa = sa, &sr = sr, &zp = zp, &wa = wa, &wr = wr, &z, &mu,
+            &el, &eps, &d, &lane](auto KB, int j, const float (&v)[NS]) {
+      constexpr int kb = KB;
+      const int jl = j - 64 * kb;
+      const float etaj = rdlane(eta[kb], jl);
+      const float invj = rdlane(inv[kb], jl);
+      // row j completes its proposal and both solves at its own column
+      if (lane == jl) {
+        acc[kb] = fmaf(1.0f, etaj, acc[kb]);
+        zp[kb] = z[kb] + fmaf(el, acc[kb], eps * xi[kb]);
+        wa[kb] = (zp[kb] - mu[kb]) - sa[kb];
+        wr[kb] = (z[kb] - mu[kb]) - sr[kb];
+      }
+      const float waj = rdlane(wa[kb], jl);
+      const float wrj = rdlane(wr[kb], jl);
+      static_for<NS>([&](auto K) {
+        if constexpr (K >= kb) {
+          const int r = 64 * K + lane;
+          if (r > j && r < d) {
+            const float uo = v[K] * invj;
+            acc[K] = fmaf(uo, etaj, acc[K]);
+            sa[K] = fmaf(uo, waj, sa[K]);
+            sr[K] = fmaf(uo, wrj, sr[K]);
+          }
+        }
+      });
+    };
+  }
+  // the step pass's inputs: chain c's rows of xprop / wa / wr / dg
+  __device__ __forceinline__ void store(const BigParams& p, const int64_t& c, const int& d, const int& lane) const {
+    static_for<NS>([&](auto K) {
+      const int r = 64 * K + lane;
+      if (r < d) {
+        p.xprop[c * d + r] = zp[K];
+        p.wa[c * d + r] = wa[K];
+        p.wr[c * d + r] = wr[K];
+        p.dg[c * d + r] = dg[K];
+      }
+    });
+  }
+};
+
+// y_v += P x_v for NV vectors at once: row k of P (= column k, P symmetric)
+// read coalesced, eight rows per batch, an fmaf chain over k in order per row
+// slot; rows k >= d read as zeros (their terms leave the chains unchanged)
+template <bool RAG, int NV, int NS>
+__device__ __forceinline__ void big_p_sweep(const float* Pm, const int& d, const int& lane, const float (&x)[NV][NS],
+                                            float (&y)[NV][NS]) {
+  static_for<NS>([&](auto KB) {
+    constexpr int kb = KB;
+    if (64 * kb < d) {
+      const int kmax = (d - 64 * kb) < 64 ? (d - 64 * kb) : 64;
+      for (int k2 = 0; k2 < kmax; k2 += 8) {
+        float pr[8][NS];
+        static_for<8>([&](auto T) {
+          const bool kin = !RAG || k2 + T < kmax;  // d % 8 == 0: kmax is a multiple of 8
+          const float* row = Pm + (int64_t)(kin ? 64 * kb + k2 + T : 0) * d;
+          static_for<NS>([&](auto K) { pr[T][K] = (kin && 64 * K + lane < d) ? row[64 * K + lane] : 0.0f; });
+        });
+        static_for<8>([&](auto T) {
+          float xk[NV];
+          static_for<NV>([&](auto V) { xk[V] = rdlane(x[V][kb], k2 + T); });
+          static_for<NS>([&](auto K) { static_for<NV>([&](auto V) { y[V][K] = fmaf(pr[T][K], xk[V], y[V][K]); }); });
+        });
+      }
+    }
+  });
+}
+
 }  // namespace
 
 // --------------------------------------------------------------- init ----
@@ -196,68 +352,27 @@ __global__ __launch_bounds__(256) void big_init_kernel(InitParams p) {
 // ------------------------------------------------------------- propose ----
 template <bool RAG, int NS>
 __global__ __launch_bounds__(256) void big_propose_kernel(BigParams p) {
-  extern __shared__ float lds_big[];
   const int d = p.d;
   const int lane = lane_id();
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
-  float* wb1 = wb0 + kColBlk * d;
-  const int64_t P = (int64_t)d * (d + 1) / 2;
-  const int64_t nw = (int64_t)gridDim.x * 4;
+  const auto [wb0, wb1, P, nw] = big_wave(d);
   for (int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x / 64; c < p.C; c += nw) {
     const float* Lc = p.in.scale + c * P;
     const int32_t it = p.in.i[c];
     const uint32_t k0 = p.in.rng_key[2 * c], k1 = p.in.rng_key[2 * c + 1];
     const float el = amh_expf(p.in.log_step_size[c]);
-    float inv[NS], xi[NS], eta[NS], zz[NS], mu[NS], acc[NS], sa[NS], sr[NS], zp[NS], wa[NS], wr[NS];
-    float pdl[NS];
-    step_noise_rows<NS>(lane, d, (uint32_t)it, k0, k1, xi);  // bit spec: amh_step_word
+    BigPropose<NS> pr;
+    float zz[NS], mu[NS];
+    step_noise_rows<NS>(lane, d, (uint32_t)it, k0, k1, pr.xi);  // bit spec: amh_step_word
+    big_diag(Lc, d, lane, pr.dg, pr.inv);
     static_for<NS>([&](auto K) {
       const int r = 64 * K + lane;
       const bool act = r < d;
-      const float dl = act ? Lc[col_off(d, act ? r : 0)] : 0.0f;
-      pdl[K] = dl;
-      inv[K] = (amh_isfinite(dl) && dl != 0.0f) ? 1.0f / dl : 0.0f;
-      eta[K] = dl * xi[K];
       zz[K] = act ? p.in.z[c * d + r] : 0.0f;
       mu[K] = act ? p.in.loc[c * d + r] : 0.0f;
-      acc[K] = sa[K] = sr[K] = zp[K] = wa[K] = wr[K] = 0.0f;
     });
-    for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&v)[NS]) {
-      constexpr int kb = KB;
-      const int jl = j - 64 * kb;
-      const float etaj = rdlane(eta[kb], jl);
-      const float invj = rdlane(inv[kb], jl);
-      // row j completes its proposal and both solves at its own column
-      if (lane == jl) {
-        acc[kb] = fmaf(1.0f, etaj, acc[kb]);
-        zp[kb] = zz[kb] + fmaf(el, acc[kb], p.eps * xi[kb]);
-        wa[kb] = (zp[kb] - mu[kb]) - sa[kb];
-        wr[kb] = (zz[kb] - mu[kb]) - sr[kb];
-      }
-      const float waj = rdlane(wa[kb], jl);
-      const float wrj = rdlane(wr[kb], jl);
-      static_for<NS>([&](auto K) {
-        if constexpr (K >= kb) {
-          const int r = 64 * K + lane;
-          if (r > j && r < d) {
-            const float uo = v[K] * invj;
-            acc[K] = fmaf(uo, etaj, acc[K]);
-            sa[K] = fmaf(uo, waj, sa[K]);
-            sr[K] = fmaf(uo, wrj, sr[K]);
-          }
-        }
-      });
-    });
-    static_for<NS>([&](auto K) {
-      const int r = 64 * K + lane;
-      if (r < d) {
-        p.xprop[c * d + r] = zp[K];
-        p.wa[c * d + r] = wa[K];
-        p.wr[c * d + r] = wr[K];
-        p.dg[c * d + r] = pdl[K];
-      }
-    });
+    pr.begin();
+    for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, pr.column(zz, mu, el, p.eps, d, lane));
+    pr.store(p, c, d, lane);
   }
 }
 
@@ -269,14 +384,9 @@ __global__ __launch_bounds__(256) void big_propose_kernel(BigParams p) {
 // at the top of its chain, so the next ones overwrite them in place.
 template <bool NEXT, bool RAG, int NS>
 __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
-  extern __shared__ float lds_big[];
   const int d = p.d;
   const int lane = lane_id();
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
-  float* wb1 = wb0 + kColBlk * d;
-  const int64_t P = (int64_t)d * (d + 1) / 2;
-  const int64_t nw = (int64_t)gridDim.x * 4;
+  const auto [wb0, wb1, P, nw] = big_wave(d);
   for (int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x / 64; c < p.C; c += nw) {
     const float* Lin = p.in.scale + c * P;
     float* Lout = p.out.scale + c * P;
@@ -293,7 +403,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
     const bool accept = u < alpha;
     const int32_t itr = it + 1;
     const int32_t n = (it < p.W) ? itr : itr - p.W;
-    const float gamma = big_gamma(p, n);
+    const float gamma = big_gamma(p.gamma_tab, p.gamma_tab_n, p.a, n);
     const float maccn = macc + (alpha - macc) / (float)n;
     const float lamn = lam + gamma * (alpha - p.target);
     const float e1 = amh_expf(lamn);
@@ -304,7 +414,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       const int r = 64 * K + lane;
       const bool act = r < d;
       dl[K] = act ? p.dg[c * d + r] : 0.0f;  // the diagonal, coalesced (propose / previous step pass)
-      inv[K] = (amh_isfinite(dl[K]) && dl[K] != 0.0f) ? 1.0f / dl[K] : 0.0f;
+      inv[K] = big_inv(dl[K]);
       const float z = act ? p.in.z[c * d + r] : 0.0f;
       const float mu = act ? p.in.loc[c * d + r] : 0.0f;
       const float zpv = act ? p.xprop[c * d + r] : 0.0f;
@@ -320,6 +430,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
       t[K] = act ? gw2[K] / Dg[K] : 0.0f;
     });
     // b_j: 64-lane exclusive scan per slot plus the carry of the slots before
+    // (asss_big_chain states these coefficients again, DESIGN.md 3.4: change both)
     float cc[NS], qq[NS];
     bool bad = false;
     float carry = 0.0f;
@@ -341,48 +452,17 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
     const bool revert = __ballot(bad) != 0ull;
     float sacc[NS];
     static_for<NS>([&](auto K) { sacc[K] = 0.0f; });
-    // next transition's propose state (big_propose_kernel on the output state)
-    float ninv[NS], nxi[NS], neta[NS], nacc[NS], nsa[NS], nsr[NS], nzp[NS], nwa[NS], nwr[NS], ndg[NS];
+    // next transition's propose pass (big_propose_kernel on the output state)
+    BigPropose<NS> nx;
     if constexpr (NEXT) {
-      step_noise_rows<NS>(lane, d, (uint32_t)itr, k0, k1, nxi);
+      step_noise_rows<NS>(lane, d, (uint32_t)itr, k0, k1, nx.xi);
       static_for<NS>([&](auto K) {
-        const int r = 64 * K + lane;
-        const bool act = r < d;
-        const float ndl = act ? (revert ? dl[K] : 1.0f * qq[K]) : 0.0f;
-        ndg[K] = ndl;
-        ninv[K] = (amh_isfinite(ndl) && ndl != 0.0f) ? 1.0f / ndl : 0.0f;
-        neta[K] = ndl * nxi[K];
-        nacc[K] = nsa[K] = nsr[K] = nzp[K] = nwa[K] = nwr[K] = 0.0f;
+        nx.dg[K] = (64 * K + lane < d) ? (revert ? dl[K] : 1.0f * qq[K]) : 0.0f;
+        nx.inv[K] = big_inv(nx.dg[K]);
       });
+      nx.begin();
     }
-    // column j of L' (rows > j in nv) into the next proposal and both solves
-    auto next_col = [&](auto KB, int j, const float (&nv)[NS]) {
-      if constexpr (NEXT) {
-        constexpr int kb = KB;
-        const int jl = j - 64 * kb;
-        const float etaj = rdlane(neta[kb], jl);
-        const float invj = rdlane(ninv[kb], jl);
-        if (lane == jl) {
-          nacc[kb] = fmaf(1.0f, etaj, nacc[kb]);
-          nzp[kb] = zn[kb] + fmaf(e1, nacc[kb], p.eps * nxi[kb]);
-          nwa[kb] = (nzp[kb] - mun[kb]) - nsa[kb];
-          nwr[kb] = (zn[kb] - mun[kb]) - nsr[kb];
-        }
-        const float waj = rdlane(nwa[kb], jl);
-        const float wrj = rdlane(nwr[kb], jl);
-        static_for<NS>([&](auto K) {
-          if constexpr (K >= kb) {
-            const int r = 64 * K + lane;
-            if (r > j && r < d) {
-              const float uo = nv[K] * invj;
-              nacc[K] = fmaf(uo, etaj, nacc[K]);
-              nsa[K] = fmaf(uo, waj, nsa[K]);
-              nsr[K] = fmaf(uo, wrj, nsr[K]);
-            }
-          }
-        });
-      }
-    };
+    auto next_col = nx.column(zn, mun, e1, p.eps, d, lane);  // references only; called under NEXT alone
     if (!revert) {
       float ac[NS], bc[NS], sv[NS];
       static_for<NS>([&](auto K) {
@@ -391,34 +471,9 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
         sv[K] = 0.0f;
       });
       for_columns<RAG, NS>(Lin, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&v)[NS]) {
-        constexpr int kb = KB;
-        const int jl = j - 64 * kb;
-        const float wsj = rdlane(ws[kb], jl), cj = rdlane(cc[kb], jl), acj = rdlane(ac[kb], jl);
-        const float bcj = rdlane(bc[kb], jl), invj = rdlane(inv[kb], jl), qj = rdlane(qq[kb], jl);
-        float* ocol = Lout + col_off(d, j) - j;
-        if (lane == jl) {
-          const float tt = fmaf(1.0f, acj, bcj * 0.0f);
-          sacc[kb] = fmaf(tt, tt, sacc[kb]);
-          ocol[j] = 1.0f * qj;
-        }
         float nv[NS];
-        static_for<NS>([&](auto K) {
-          nv[K] = 0.0f;
-          if constexpr (K >= kb) {
-            const int r = 64 * K + lane;
-            if (r > j && r < d) {
-              const float uo = v[K] * invj;
-              sv[K] = fmaf(uo, wsj, sv[K]);
-              const float w = delta[K] - sv[K];
-              const float un = fmaf(cj, w, uo);
-              const float tt = fmaf(uo, acj, bcj * w);
-              sacc[K] = fmaf(tt, tt, sacc[K]);
-              nv[K] = un * qj;
-              ocol[r] = nv[K];
-            }
-          }
-        });
-        next_col(KB, j, nv);
+        big_update_column<KB>(j, v, ws, cc, qq, ac, bc, inv, delta, sv, sacc, Lout, d, lane, nv);
+        if constexpr (NEXT) next_col(KB, j, nv);
       });
     } else {
       // factor kept (arwmh.py:191): copied verbatim; as_change = ||L (e1 - e0)||_F
@@ -445,7 +500,7 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
             }
           }
         });
-        next_col(KB, j, v);
+        if constexpr (NEXT) next_col(KB, j, v);
       });
     }
     const float asc = sqrtf(big_sum(sacc));
@@ -455,14 +510,9 @@ __global__ __launch_bounds__(256) void big_step_kernel(BigParams p) {
         p.out.z[c * d + r] = zn[K];
         p.out.loc[c * d + r] = mun[K];
         if (p.col_z != nullptr) p.col_z[c * d + r] = zn[K];
-        if constexpr (NEXT) {
-          p.xprop[c * d + r] = nzp[K];
-          p.wa[c * d + r] = nwa[K];
-          p.wr[c * d + r] = nwr[K];
-          p.dg[c * d + r] = ndg[K];
-        }
       }
     });
+    if constexpr (NEXT) nx.store(p, c, d, lane);
     if (lane == 0) {
       p.out.i[c] = itr;
       p.out.potential_energy[c] = accept ? pep : pe;
@@ -697,7 +747,9 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
   static_for<NS>([&](auto K) { v[K] = degen ? 0.0f : v[K] / nv; });
   vd = degen ? 0.0f : vd / nv;
   // ---- S z = 2 (x - mu) / den, S v = (S v_raw - dot S z) / |v|; U^-1 z, U^-1 v
-  float Sz[NS], Sv[NS], Wz[NS], Wv[NS], gm[NS], Pa[NS], Pb[NS], Pg[NS];
+  float cir[3][NS], Pc[3][NS], Wz[NS], Wv[NS];  // (S z, S v, g) and P times each
+  float(&Sz)[NS] = cir[0], (&Sv)[NS] = cir[1], (&gm)[NS] = cir[2];
+  float(&Pa)[NS] = Pc[0], (&Pb)[NS] = Pc[1], (&Pg)[NS] = Pc[2];
   static_for<NS>([&](auto K) {
     const int r = 64 * K + lane;
     const bool act = r < d;
@@ -710,30 +762,7 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
     gm[K] = act ? mu[K] - m[act ? r : 0] : 0.0f;
     Pa[K] = Pb[K] = Pg[K] = 0.0f;
   });
-  // ---- P a, P b, P g: row k of P (= column k) coalesced, k in order
-  static_for<NS>([&](auto KB) {
-    constexpr int kb = KB;
-    if (64 * kb < d) {
-      const int kmax = (d - 64 * kb) < 64 ? (d - 64 * kb) : 64;
-      for (int k2 = 0; k2 < kmax; k2 += 8) {
-        float pr[8][NS];  // rows k >= d read as zeros (their terms leave the chains unchanged)
-        static_for<8>([&](auto T) {
-          const bool kin = !RAG || k2 + T < kmax;  // d % 8 == 0: kmax is a multiple of 8
-          const float* row = Pm + (int64_t)(kin ? 64 * kb + k2 + T : 0) * d;
-          static_for<NS>([&](auto K) { pr[T][K] = (kin && 64 * K + lane < d) ? row[64 * K + lane] : 0.0f; });
-        });
-        static_for<8>([&](auto T) {
-          const int kl = k2 + T;
-          const float sa = rdlane(Sz[kb], kl), sb = rdlane(Sv[kb], kl), sg = rdlane(gm[kb], kl);
-          static_for<NS>([&](auto K) {
-            Pa[K] = fmaf(pr[T][K], sa, Pa[K]);
-            Pb[K] = fmaf(pr[T][K], sb, Pb[K]);
-            Pg[K] = fmaf(pr[T][K], sg, Pg[K]);
-          });
-        });
-      }
-    }
-  });
+  big_p_sweep<RAG>(Pm, d, lane, cir, Pc);  // P a, P b, P g
   // the point at angle (cs, sn) of the slice circle: x and U
   auto eval = [&](float cs, float sn, float (&xo)[NS], float& om) -> float {
     om = 1.0f - ((zd * cs) + (vd * sn));
@@ -849,30 +878,8 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
         sv[K] = sacc[K] = 0.0f;
       });
       for_columns<RAG, NS>(Lc, d, P, wb0, wb1, lane, [&](auto KB, int j, const float (&vv)[NS]) {
-        constexpr int kb = KB;
-        const int jl = j - 64 * kb;
-        const float wsj = rdlane(ws[kb], jl), cj = rdlane(cc[kb], jl), acj = rdlane(ac[kb], jl);
-        const float bcj = rdlane(bc[kb], jl), invj = rdlane(inv[kb], jl), qj = rdlane(qq[kb], jl);
-        float* ocol = Lout + col_off(d, j) - j;
-        if (lane == jl) {
-          const float t0 = fmaf(1.0f, acj, bcj * 0.0f);
-          sacc[kb] = fmaf(t0, t0, sacc[kb]);
-          ocol[j] = 1.0f * qj;
-        }
-        static_for<NS>([&](auto K) {
-          if constexpr (K >= kb) {
-            const int r = 64 * K + lane;
-            if (r > j && r < d) {
-              const float uo = vv[K] * invj;
-              sv[K] = fmaf(uo, wsj, sv[K]);
-              const float w = delta[K] - sv[K];
-              const float un = fmaf(cj, w, uo);
-              const float t1 = fmaf(uo, acj, bcj * w);
-              sacc[K] = fmaf(t1, t1, sacc[K]);
-              ocol[r] = un * qj;
-            }
-          }
-        });
+        float nv[NS];
+        big_update_column<KB>(j, vv, ws, cc, qq, ac, bc, inv, delta, sv, sacc, Lout, d, lane, nv);
       });
       sdiff = sqrtf(big_sum(sacc));
     } else if (Lout != Lc) {  // factor kept (asss.py:255): copied verbatim
@@ -901,32 +908,25 @@ __device__ __forceinline__ void asss_big_chain(const float* Lc, float* Lout, con
 // ASSS.sample: one transition of every chain per launch (host loops n_steps)
 template <bool RAG, int NS>
 __global__ __launch_bounds__(256) void asss_big_step_kernel(StepParams p) {
-  extern __shared__ float lds_big[];
   const int d = p.d;
   const int lane = lane_id();
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
-  float* wb1 = wb0 + kColBlk * d;
-  const int64_t P = (int64_t)d * (d + 1) / 2;
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  typedef __attribute__((address_space(4))) const float cf;
+  const auto [wb0, wb1, P, nw] = big_wave(d);
   for (int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x / 64; c < p.C; c += nw) {
     const float* Lc = p.in.scale + c * P;
     float* Lo = p.out.scale + c * P;
     const int32_t it = p.in.i[c];
     const uint32_t k0 = p.in.rng_key[2 * c], k1 = p.in.rng_key[2 * c + 1];
     float dl[NS], inv[NS], x[NS], mu[NS];
+    big_diag(Lc, d, lane, dl, inv);
     static_for<NS>([&](auto K) {
       const int r = 64 * K + lane;
       const bool act = r < d;
-      dl[K] = act ? Lc[col_off(d, act ? r : 0)] : 0.0f;
-      inv[K] = (amh_isfinite(dl[K]) && dl[K] != 0.0f) ? 1.0f / dl[K] : 0.0f;
       x[K] = act ? p.in.z[c * d + r] : 0.0f;
       mu[K] = act ? p.in.loc[c * d + r] : 0.0f;
     });
     const int32_t itr = it + 1;
     const int32_t n = (it < p.W) ? itr : itr - p.W;
-    const float gamma = (n < p.gamma_tab_n) ? ((const cf*)p.gamma_tab)[n] : amh_lr_gamma(n, p.a);
+    const float gamma = big_gamma(p.gamma_tab, p.gamma_tab_n, p.a, n);
     float pe = p.in.potential_energy[c];
     float asc = 0.0f;
     asss_big_chain<true, RAG, NS>(Lc, Lo, dl, inv, x, mu, pe, asc, it, k0, k1, d, P, p.eps, p.W, gamma, p.model, wb0, wb1,
@@ -955,22 +955,12 @@ __global__ __launch_bounds__(256) void asss_big_step_kernel(StepParams p) {
 // stream position the step index
 template <bool RAG, int NS>
 __global__ __launch_bounds__(256) void asss_big_pnx_kernel(AsssPnxParams p) {
-  extern __shared__ float lds_big[];
   const int d = p.d;
   const int lane = lane_id();
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
-  float* wb1 = wb0 + kColBlk * d;
-  const int64_t P = (int64_t)d * (d + 1) / 2;
-  const int64_t nw = (int64_t)gridDim.x * 4;
+  const auto [wb0, wb1, P, nw] = big_wave(d);
   const int64_t C = p.n_points * p.n_samples;
   float dl[NS], inv[NS];
-  static_for<NS>([&](auto K) {
-    const int r = 64 * K + lane;
-    const bool act = r < d;
-    dl[K] = act ? p.scale[col_off(d, act ? r : 0)] : 0.0f;
-    inv[K] = (amh_isfinite(dl[K]) && dl[K] != 0.0f) ? 1.0f / dl[K] : 0.0f;
-  });
+  big_diag(p.scale, d, lane, dl, inv);
   for (int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x / 64; c < C; c += nw) {
     const int64_t pt = c / p.n_samples;
     const amh_u32x4 kk = amh_philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), 0u, AMH_TAG_SPLIT, p.key0, p.key1);
@@ -1001,14 +991,9 @@ __global__ __launch_bounds__(256) void asss_big_pnx_kernel(AsssPnxParams p) {
 // MFMA kernel's tile order (pot_gaussian_big).
 template <bool RAG, int NS>
 __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
-  extern __shared__ float lds_big[];
   const int d = p.d;
   const int lane = lane_id();
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-  float* wb0 = lds_big + (size_t)wv * 2 * kColBlk * d;
-  float* wb1 = wb0 + kColBlk * d;
-  const int64_t P = (int64_t)d * (d + 1) / 2;
-  const int64_t nw = (int64_t)gridDim.x * 4;
+  const auto [wb0, wb1, P, nw] = big_wave(d);
   const int64_t C = p.n_points * p.n_samples;
   const float* m = p.model.data;
   const float* Pm = p.model.data + d;
@@ -1016,33 +1001,16 @@ __global__ __launch_bounds__(256) void big_pnx_kernel(PnxParams p) {
   const float el = amh_expf(p.log_step_size);
   // U(zz) = 0.5 sum_r D_r Y_r + c0, Y = P D, D = zz - m
   auto potential = [&](const float (&zz)[NS]) -> float {
-    float D[NS], Y[NS];
+    float D[1][NS], Y[1][NS];
     static_for<NS>([&](auto K) {
       const int r = 64 * K + lane;
       const bool act = r < d;
-      D[K] = act ? zz[K] - m[act ? r : 0] : 0.0f;
-      Y[K] = 0.0f;
+      D[0][K] = act ? zz[K] - m[act ? r : 0] : 0.0f;
+      Y[0][K] = 0.0f;
     });
-    static_for<NS>([&](auto KB) {
-      constexpr int kb = KB;
-      if (64 * kb < d) {
-        const int kmax = (d - 64 * kb) < 64 ? (d - 64 * kb) : 64;
-        for (int k2 = 0; k2 < kmax; k2 += 8) {
-          float pr[8][NS];  // rows k >= d read as zeros
-          static_for<8>([&](auto T) {
-            const bool kin = !RAG || k2 + T < kmax;  // d % 8 == 0: kmax is a multiple of 8
-            const float* row = Pm + (int64_t)(kin ? 64 * kb + k2 + T : 0) * d;  // row k = column k (P symmetric)
-            static_for<NS>([&](auto K) { pr[T][K] = (kin && 64 * K + lane < d) ? row[64 * K + lane] : 0.0f; });
-          });
-          static_for<8>([&](auto T) {
-            const float dk = rdlane(D[kb], k2 + T);
-            static_for<NS>([&](auto K) { Y[K] = fmaf(pr[T][K], dk, Y[K]); });
-          });
-        }
-      }
-    });
+    big_p_sweep<RAG>(Pm, d, lane, D, Y);
     float q[NS];
-    static_for<NS>([&](auto K) { q[K] = (64 * K + lane < d) ? D[K] * Y[K] : 0.0f; });
+    static_for<NS>([&](auto K) { q[K] = (64 * K + lane < d) ? D[0][K] * Y[0][K] : 0.0f; });
     // tile order: 32-row tiles in order, each (ph_0 + ph_1), ph_h the
     // sequential sum of rows 32 I + (g & 3) + 8 (g >> 2) + 4 h, g = 0..15
     float S = 0.0f;
@@ -1135,43 +1103,35 @@ hipError_t run_big_init(const InitParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 static size_t stream_lds(int d) { return (size_t)4 * 2 * kColBlk * d * sizeof(float); }
-#define AMH_BY_NS(NAME, ...) \
-  (ns == 2 ? NAME<__VA_ARGS__, 2> : (ns == 3 ? NAME<__VA_ARGS__, 3> : NAME<__VA_ARGS__, 4>))
-hipError_t run_big_propose(const BigParams& p, hipStream_t s) {
-  const bool rag = p.d % kColBlk != 0;
+// One wave per chain over n chains of a streaming kernel: pick(RAG, NS) gives
+// the instantiation for p.d (ragged last block, row slots per lane).
+template <class Params, class Pick>
+static hipError_t launch_streaming(const Params& p, int64_t n, hipStream_t s, Pick pick) {
   const int ns = row_slots(p.d);
-  auto k = rag ? AMH_BY_NS(big_propose_kernel, true) : AMH_BY_NS(big_propose_kernel, false);
-  hipLaunchKernelGGL(k, dim3(wave_grid(p.C)), dim3(256), stream_lds(p.d), s, p);
+  auto by_ns = [&](auto RAG) {
+    return ns == 2 ? pick(RAG, std::integral_constant<int, 2>{})
+                   : (ns == 3 ? pick(RAG, std::integral_constant<int, 3>{}) : pick(RAG, std::integral_constant<int, 4>{}));
+  };
+  auto k = (p.d % kColBlk != 0) ? by_ns(std::true_type{}) : by_ns(std::false_type{});
+  hipLaunchKernelGGL(k, dim3(wave_grid(n)), dim3(256), stream_lds(p.d), s, p);
   return hipGetLastError();
+}
+hipError_t run_big_propose(const BigParams& p, hipStream_t s) {
+  return launch_streaming(p, p.C, s, [](auto RAG, auto NS) { return big_propose_kernel<RAG, NS>; });
 }
 hipError_t run_big_step(const BigParams& p, hipStream_t s, bool next) {
-  const bool rag = p.d % kColBlk != 0;
-  const int ns = row_slots(p.d);
-  auto k = next ? (rag ? AMH_BY_NS(big_step_kernel, true, true) : AMH_BY_NS(big_step_kernel, true, false))
-                : (rag ? AMH_BY_NS(big_step_kernel, false, true) : AMH_BY_NS(big_step_kernel, false, false));
-  hipLaunchKernelGGL(k, dim3(wave_grid(p.C)), dim3(256), stream_lds(p.d), s, p);
-  return hipGetLastError();
+  return next ? launch_streaming(p, p.C, s, [](auto RAG, auto NS) { return big_step_kernel<true, RAG, NS>; })
+              : launch_streaming(p, p.C, s, [](auto RAG, auto NS) { return big_step_kernel<false, RAG, NS>; });
 }
 hipError_t run_asss_big_step(const StepParams& p, hipStream_t s) {
-  const bool rag = p.d % kColBlk != 0;
-  const int ns = row_slots(p.d);
-  auto k = rag ? AMH_BY_NS(asss_big_step_kernel, true) : AMH_BY_NS(asss_big_step_kernel, false);
-  hipLaunchKernelGGL(k, dim3(wave_grid(p.C)), dim3(256), stream_lds(p.d), s, p);
-  return hipGetLastError();
+  return launch_streaming(p, p.C, s, [](auto RAG, auto NS) { return asss_big_step_kernel<RAG, NS>; });
 }
 hipError_t run_big_pnx(const PnxParams& p, hipStream_t s) {
-  const bool rag = p.d % kColBlk != 0;
-  const int ns = row_slots(p.d);
-  auto k = rag ? AMH_BY_NS(big_pnx_kernel, true) : AMH_BY_NS(big_pnx_kernel, false);
-  hipLaunchKernelGGL(k, dim3(wave_grid(p.n_points * p.n_samples)), dim3(256), stream_lds(p.d), s, p);
-  return hipGetLastError();
+  return launch_streaming(p, p.n_points * p.n_samples, s, [](auto RAG, auto NS) { return big_pnx_kernel<RAG, NS>; });
 }
 hipError_t run_asss_big_pnx(const AsssPnxParams& p, hipStream_t s) {
-  const bool rag = p.d % kColBlk != 0;
-  const int ns = row_slots(p.d);
-  auto k = rag ? AMH_BY_NS(asss_big_pnx_kernel, true) : AMH_BY_NS(asss_big_pnx_kernel, false);
-  hipLaunchKernelGGL(k, dim3(wave_grid(p.n_points * p.n_samples)), dim3(256), stream_lds(p.d), s, p);
-  return hipGetLastError();
+  return launch_streaming(p, p.n_points * p.n_samples, s,
+                          [](auto RAG, auto NS) { return asss_big_pnx_kernel<RAG, NS>; });
 }
 hipError_t run_big_potential(const PotParams& p, hipStream_t s) {
   const int64_t blocks = (p.n + kPotChains - 1) / kPotChains;

@@ -92,6 +92,28 @@ def test_asss_fused_and_collect_bitexact(kind, d, C, gpu, orc):
     assert_bitequal(st, ost, f"{kind} in place")
 
 
+@pytest.mark.parametrize("d", [100, 192])
+def test_asss_large_d_in_place_from_init(d, gpu, orc):
+    """ASSS.sample_ from init with num_warmup = 1 at large d: in place the
+    output factor is the input factor, so the kept factor of steps 1 and 2
+    (gamma = 1) takes the branch without the copy pass, and pass D of steps 3
+    and 4 streams L' over the factor it reads."""
+    C, W, n = 9, 1, 4
+    k, st, om, ost = _init("gaussian", C, orc, d=d, num_warmup=W)
+    one = ost.copy()
+    for t in range(1, n + 1):
+        before, z = one.scale.copy(), one.z.copy()
+        orc.asss_step(om, one, 1, num_warmup=W)
+        kept = np.array_equal(before.view(np.uint32), one.scale.view(np.uint32))
+        assert kept == (t <= 2), f"d={d} step {t}: factor kept = {kept}"
+        assert np.all(np.any(z != one.z, axis=1)), f"d={d} step {t}: a chain did not move"
+    k.sample_(st, n)
+    orc.asss_step(om, ost, n, num_warmup=W)
+    torch.cuda.synchronize()
+    assert_bitequal(st, ost, f"d={d} in place")
+    assert_bitequal(st, one, f"d={d} in place against single oracle steps")
+
+
 def test_asss_sample_pnx_bitexact(gpu, orc):
     from kernels_amd import PRNGKey
     k, st, om, ost = _init("eight_schools", 64, orc)

@@ -141,6 +141,48 @@ def test_big_dim_bitexact(d, C, steps, gpu, orc):
     np.testing.assert_array_equal(cz.cpu().numpy().view(np.uint32), ocz[1::2].view(np.uint32))
 
 
+@pytest.mark.parametrize("d", [72, 100, 192, 256])
+def test_big_dim_fused_from_init_bitexact(d, gpu, orc):
+    """One five-step launch from init with num_warmup = 1: gamma = 1 at steps
+    1 and 2, so the factor is kept there while the launch also forms the next
+    proposal (big_step_kernel<NEXT>'s keep-L branch); steps 3 to 5 update it.
+    log_step_size = -2 so that some, not all, of the nine chains accept in
+    every step (three blocks of four waves, the last one partial).  State,
+    both collections and accept_count bit for bit, out of place and in place."""
+    C, W, n = 9, 1, 5
+
+    def start():
+        k, st, om, ost = _init("gaussian", C, gpu, orc, d=d, num_warmup=W)
+        st.adapt_state.log_step_size.fill_(-2.0)
+        ost.log_step_size[:] = -2.0
+        return k, st, om, ost
+
+    k, st, om, ost = start()
+    # the conditions of the case, from the oracle alone, one transition at a time
+    one, pes = ost.copy(), []
+    for t in range(1, n + 1):
+        before, a1 = one.scale.copy(), np.zeros(C, np.int32)
+        orc.step(om, one, 1, num_warmup=W, accept_count=a1)
+        pes.append(one.potential_energy.copy())
+        kept = np.array_equal(before.view(np.uint32), one.scale.view(np.uint32))
+        assert kept == (t <= 2), f"d={d} step {t}: factor kept = {kept}"
+        assert 1 <= int(a1.sum()) <= C - 1, f"d={d} step {t}: {int(a1.sum())} of {C} chains accept"
+    acc = np.zeros(C, np.int32)
+    st2, cz, cp = k.run(st, n, thinning=1, collect_z=True, collect_pe=True)
+    ocz = orc.step(om, ost, n, num_warmup=W, collect_z=True, accept_count=acc)
+    torch.cuda.synchronize()
+    assert_state_bitequal(st2, ost, f"d={d} run")
+    assert_state_bitequal(st2, one, f"d={d} run against single oracle steps")
+    np.testing.assert_array_equal(cz.cpu().numpy().view(np.uint32), ocz.view(np.uint32))
+    np.testing.assert_array_equal(cp.cpu().numpy().view(np.uint32), np.stack(pes).view(np.uint32))
+    np.testing.assert_array_equal(k.accept_count.cpu().numpy(), acc)
+    k, st, om, _ = start()
+    k.sample_(st, n)
+    torch.cuda.synchronize()
+    assert_state_bitequal(st, ost, f"d={d} in place")
+    np.testing.assert_array_equal(k.accept_count.cpu().numpy(), acc)
+
+
 def test_sample_pnx_bitexact(gpu, orc):
     from kernels_amd import PRNGKey
     k, st, om, ost = _init("gaussian", 4, gpu, orc, d=16)
