@@ -424,3 +424,39 @@ def pooled_f64_blocks(impl, model, keys, K, W, blocks=3):
         assert not pnp.worst(r), (f"block {b + 1}", pnp.worst(r))
         res.append(r)
     return res
+
+
+# ------------------------------------------- grid caps and item hand-over ----
+# One pass of a capped grid-stride launch, in items (tests/test_gpu_steady.py,
+# tests/test_gpu_steady_pnx.py).  Read from the launchers; every test that
+# relies on one asserts that its size crosses it, so a raised cap fails there.
+BIG_CAP = 4096 * 4    # amh_big.hip wave_grid: 4,096 blocks x 4 waves, one chain per wave
+GROUP_CAP = 8192 * 4  # amh_kernels.hip grid_for and its copies in amh_asss.hip, amh_asss_ext.hip and
+#                       amh_split.hip: 8,192 blocks x 4 waves, one item of CPW = 64 / G chains per wave
+
+
+def items_per_wave(C, cap, cpw=1):
+    """Items the busiest wave of a capped launch takes for C chains at cpw
+    chains per item: wave w walks items w, w + cap, ..."""
+    n_items = -(-C // cpw)
+    return -(-n_items // cap)
+
+
+def state_rows(state, lo, hi):
+    """Chains [lo, hi) of a product state (ARWMH or ASSS namedtuples): the same
+    types, every leaf sliced on the device, so only the slice reaches the host."""
+    a = state.adapt_state
+    return type(state)(*[type(a)(*[t[lo:hi] for t in a]) if f is a else f[lo:hi] for f in state])
+
+
+def assert_chains_bitequal(got, ref, cap, cpw, what=""):
+    """[C, d] (or [C]) arrays bit for bit; a mismatch is reported by chain with
+    the item, the wave and the pass of the capped launch that produced it."""
+    got = got.detach().cpu().numpy() if hasattr(got, "detach") else np.asarray(got)
+    ref = np.asarray(ref)
+    C = got.shape[0]
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    ne = (got.view(np.uint32) != ref.view(np.uint32)).reshape(C, -1).any(axis=1)
+    bad = np.flatnonzero(ne)
+    where = [f"chain {c}: item {c // cpw} = wave {(c // cpw) % cap}, pass {(c // cpw) // cap}" for c in bad[:4]]
+    assert bad.size == 0, f"{what}: {bad.size} of {C} chains differ; first {where}"

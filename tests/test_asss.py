@@ -54,6 +54,9 @@ def _step_compare(kind, pre, orc, C=48, d=None):
                                     ("diamonds", None), ("mixture", 1), ("mixture", 3),
                                     # large d (asss_step_big1: streamed factor, potential along the circle)
                                     ("gaussian", 96), ("gaussian", 128), ("gaussian", 100), ("gaussian", 97),
+                                    # three and four row slots per lane (big_sum's slot order, the
+                                    # scan carry across slots)
+                                    ("gaussian", 150), ("gaussian", 160), ("gaussian", 256),
                                     # the GLM models at K = 7 / 31, N = 77
                                     ("logistic_n77", 8), ("logistic_n77", 32),
                                     ("poisson_n77", 8), ("poisson_n77", 32)])

@@ -104,6 +104,9 @@ def test_nan_potential_rejects():
                                       # large d off the 32-multiples: a ragged MFMA tile,
                                       # dword-DMA column blocks, an odd d
                                       ("gaussian", 72), ("gaussian", 100), ("gaussian", 97),
+                                      # three row slots per lane (129 <= d <= 192): big_sum's slot
+                                      # order and the scan carry across slots, dword and dwordx4 DMA
+                                      ("gaussian", 150), ("gaussian", 160),
                                       # the GLM models at K = 7 / 31, N = 77 (model 4's tolerances)
                                       ("logistic_n77", 8), ("logistic_n77", 32),
                                       ("poisson_n77", 8), ("poisson_n77", 32)])
